@@ -8,23 +8,28 @@ step    : ONE full forward of MixLinear_GEMM over one 512-token batch already re
           (i)+(ii) fused extract/zero/absmax/quantise kernel  +  (iii)+(iv) int8 MFMA GEMM with fused dequant,
           fp16 outlier tail and (absent for Llama) bias.  Each step gets its own pristine activation buffer (the
           operator zeroes outlier columns in place, as the reference does), so no restore copy sits in the timed region.
-timing  : the K steps are ONE hipGraph; barrier + synchronize on both sides of the timed region; the clock is HIP events on the launch
-          stream (the host wall time around the same region is reported beside it); MAX over ranks.
+timing  : the timed region is exactly the K = --steps steps: R back-to-back replays of a G-step hipGraph, G = max(min(K, 20), K // --replays),
+          R = K // G, plus one replay of a graph of the K - R*G remaining steps when G does not divide K; barrier + synchronize in
+          front of it; the clock is HIP events on the launch stream, one pair around every replay; MAX over ranks.
           The metric is SUSTAINED throughput, and an MI355X needs 15-25 ms of continuous work to reach the clock it sustains
           (measured: the same graph replayed from idle runs 33-34 us per step for its first 2-3 ms, 30.9 us from ~12 ms on), so
-          after the W warm-up steps and before the timed region the captured graph is replayed, untimed, for ~40 ms
-          (CLOCK_SETTLE_MS; the inputs are restored afterwards).  One replay of a 20-step graph is a 0.6 ms sample that also carries
-          the graph-launch latency (~45 us per replay from an idle stream: BENCH_r04's eager loop beat its own graph figure), so the
-          timed region is --replays (31) back-to-back replays of the K-step graph, each between its own pair of events with the device
-          never idle between them, and ms_per_step = MEDIAN replay / K (timing.replay_ms_min / median / max carry the spread; the
-          single-replay figure of rounds 1-4 and the first replay after idle are reported beside it).  A step computes what it always did.
+          after the W warm-up steps the captured graph is replayed, untimed, for ~40 ms (CLOCK_SETTLE_MS), queued directly in front of
+          the timed replays.  A replay from an idle stream also carries the graph-launch latency (~45 us: BENCH_r04's eager loop beat
+          its own graph figure), so nothing in front of the timed replays lets the device idle; the inputs are restored in front of every
+          replay, outside its event pair.  ms_per_step = MEDIAN replay / G (timing.replay_ms_min / median / max carry the spread).
+          A step computes what it always did.
+--full  : everything beyond the headline, off by default: the self-check against a Linear over the dequantised operands, the
+          single-replay figure of rounds 1-4, the GEMM + epilogue alone under the same protocol (`roofline`), the secondary timings
+          (eager loop, cold weights, MLP block, BASELINE configs 2-4; --no-secondary drops them) and the CPU baseline (--no-cpu-baseline).
+--dump-outputs DIR : after the timed region, y of the last timed step (rank 0) as DIR/y.npy in float32; above 63 MB a fixed seeded
+          sample of its rows, whose indices go to DIR/y_rows.npy (float64).  Same arguments, same inputs: two builds compare output for output.
 N GPUs  : one process per GPU, no data-path collective, one all_gather of {elapsed, flops} at the end.
           --scaling weak (default): every rank runs the same K steps on its own 512-token batches;
           --scaling strong: the 512 rows are split over the ranks (bench.shard_rows), weights replicated.
           value = sum of FLOPs over ranks / max time.  `python bench.py --gpus N` launches its N ranks itself; under
           `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` it uses the ranks it was given.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--shape K,N] [--batch M]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--shape K,N] [--batch M] [--full] [--dump-outputs DIR]
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -45,6 +50,8 @@ M, K, N = 512, 4096, 11008   # BASELINE.json metric shape (Llama-2-7b up/gate pr
 OUTLIER_FRAC = 0.01
 SIGMA = 6
 CLOCK_SETTLE_MS = 40.0       # untimed graph replays in front of the timed region: the chip's clock needs this long to settle under load
+GRAPH_STEPS = 20             # steps per captured graph while K allows (rounds 1-6 timed 20-step graphs: the driver's --steps 20)
+DUMP_BYTES = 63 << 20        # --dump-outputs budget (64 MB in all, headers included)
 
 
 def timed_replays(graph, stream, replays, restore=None):
@@ -52,7 +59,7 @@ def timed_replays(graph, stream, replays, restore=None):
     queued before the host waits once: the device goes from one replay straight into the next (`restore()`, when given, puts the inputs
     back between two replays, OUTSIDE every event pair - the forward zeroes outlier columns in place).  Returns the list of per-replay
     milliseconds.  A single replay of a 20-step graph is a 0.6 ms sample with >= 7 % run-internal scatter; the median of
-    >= 31 such samples is what bench.py reports."""
+    such samples is the figure."""
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(replays)]
     with torch.cuda.stream(stream):                                 # restore, events and replays all ordered on the launch stream
         for a, b in ev:
@@ -91,19 +98,49 @@ def conditioned_replay(graph, stream, restore=None, settle_ms=None, replays=9):
     return median(timed_replays(graph, stream, replays, restore)), first_ms, reps
 
 
+def split_steps(steps, replays):
+    """(G, R, tail): the `steps` timed steps as R replays of a G-step graph plus one graph of `tail` steps (R*G + tail == steps).  G is
+    GRAPH_STEPS (all the steps, when fewer) up to `replays` x GRAPH_STEPS steps and steps // `replays` beyond, so a long run stays about
+    `replays` samples of the same protocol instead of more and shorter ones."""
+    g = max(min(steps, GRAPH_STEPS), steps // max(1, replays))
+    return g, steps // g, steps % g
+
+
+def output_sample(y, budget=DUMP_BYTES, seed=0):
+    """{name: host array} for --dump-outputs: y in float32, or - when that exceeds `budget` bytes - a fixed seeded sample of its rows
+    (ascending) together with their indices (float64)."""
+    rows, cols = y.shape
+    if rows * cols * 4 <= budget:
+        return {"y": y.float().cpu().numpy()}
+    keep = max(1, budget // (cols * 4 + 8))
+    idx = torch.randperm(rows, generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+    return {"y": y[idx.to(y.device)].float().cpu().numpy(), "y_rows": idx.double().numpy()}
+
+
+def dump_outputs(out_dir, arrays):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20, help="forwards per timed region = per hipGraph (the driver runs --steps 20 --warmup 5)")
+    ap.add_argument("--steps", type=int, default=20, help="timed forwards: the timed region is exactly these steps (the driver runs --steps 20 --warmup 5)")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--replays", type=int, default=31, help="back-to-back timed replays of the K-step graph; the median is reported")
+    ap.add_argument("--replays", type=int, default=31, help="the timed steps are cut into about this many graph replays (at least 20 steps each); "
+                                                            "the median replay is reported")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
     ap.add_argument("--shape", default=None, help="K,N of the Linear (default 4096,11008); e.g. 8192,28672 for BASELINE config 3")
     ap.add_argument("--batch", type=int, default=None, help="token rows M (default 512)")
     ap.add_argument("--bit", type=int, choices=[8, 4], default=8, help="8: W8A8O16 (the metric); 4: W4A4O16, 128 static fp16 columns (BASELINE config 2)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the eager / cold-weights secondary timings")
+    ap.add_argument("--full", action="store_true", help="also the self-check, the GEMM-alone roofline, the single-replay figure, the secondary "
+                                                        "timings and the CPU baseline (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write y of the last timed step as DIR/y.npy (float32, <= 64 MB)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the eager / cold-weights / MLP-block / config secondary timings")
     ap.add_argument("--no-graph", action="store_true", help="launch every step eagerly from Python instead of one hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--backend", default="nccl")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: exercise the launch / rendezvous / gather path with synthetic per-rank timings (CPU, gloo)")
@@ -417,7 +454,10 @@ def main(argv=None):
     bit = args.bit
     lin, cache, layer = build_layer(device, rows, bit=bit)
     steps, warm = args.steps, args.warmup
-    cols, base, pristine = make_batches(steps, rows, device, rank)
+    if steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    glen, nrep, tail = (steps, 0, 0) if args.no_graph else split_steps(steps, args.replays)
+    cols, base, pristine = make_batches(glen, rows, device, rank)
     nbuf = pristine.shape[0]
 
     # outlier prediction warm-up: the first cache.stop (=2) forwards discover and freeze `ind` (host syncs allowed here)
@@ -428,8 +468,9 @@ def main(argv=None):
     assert layer.add_outliers is False
     n_ind = int(layer.ind.numel())
 
-    # quick self-check against a Linear over the dequantised operands on the GPU (the CPU-oracle parity lives in tests/)
-    with torch.no_grad():
+    # --full: quick self-check against a Linear over the dequantised operands on the GPU (the CPU-oracle parity lives in tests/)
+    max_abs_err = None
+    if args.full:
         xz = base.clone()
         q, xo = mixlib.QuantFused(xz, layer.ind, cache.x_scale, bit, SIGMA)
         if bit == 4:                                            # nibbles -> signed values, even column in the low nibble
@@ -451,56 +492,73 @@ def main(argv=None):
     def one_step(i):
         return layer(pristine[i % nbuf], None, True)
 
+    def capture(n):                                             # a graph of steps 0 .. n-1 and the output of its last step
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=side):
+            for i in range(n):
+                y = one_step(i)
+        return g, y
+
+    restore_inputs = lambda: pristine.copy_(base.unsqueeze(0).expand_as(pristine))
     side = torch.cuda.Stream(device=device)
-    graph = None
-    first_replay_ms, settle_reps = None, 0
+    graph = tail_graph = None
+    first_replay_ms, settle_reps, replay_ms, tail_ms, region_ms = None, 0, None, None, None
     with torch.cuda.stream(side):
-        for i in range(min(warm, steps)):                       # untimed warm-up steps (on buffers restored below)
+        for i in range(warm):                                   # untimed warm-up steps (on buffers restored below)
             one_step(i)
         torch.cuda.synchronize()
-        pristine.copy_(base.unsqueeze(0).expand_as(pristine))
+        restore_inputs()
         if not args.no_graph:
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side):
-                for i in range(steps):
-                    one_step(i)
+            graph, y_last = capture(glen)
+            if tail:
+                tail_graph, y_last = capture(tail)
             torch.cuda.synchronize()
             f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             f0.record(side)
             graph.replay()                                      # first replay after idle: graph upload, cold clocks (reported, not `value`)
             f1.record(side)
+            if tail_graph is not None:
+                tail_graph.replay()                             # (its upload, out of the timed region)
             torch.cuda.synchronize()
             first_replay_ms = f0.elapsed_time(f1)
             settle_reps = min(4000, max(1, int(CLOCK_SETTLE_MS / max(first_replay_ms, 1e-3))))
-            for _ in range(settle_reps):                        # untimed: bring the chip to the clock it sustains under this load
-                graph.replay()
-            torch.cuda.synchronize()
-            pristine.copy_(base.unsqueeze(0).expand_as(pristine))
-        restore_inputs = lambda: pristine.copy_(base.unsqueeze(0).expand_as(pristine))
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
         barrier(world, device)
         torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        replay_ms = None
         if graph is not None:
-            # the K-step graph replayed `--replays` times back to back, each replay between its own pair of events (the device never
-            # idles between them; the inputs are restored between replays, outside the event pairs): the MEDIAN replay is the figure
-            replay_ms = timed_replays(graph, side, args.replays, restore_inputs)
-            host_elapsed = (time.perf_counter() - t0) / args.replays
-            elapsed = median(replay_ms) * 1e-3
+            # untimed: bring the chip to the clock it sustains under this load, queued right in front of the timed replays so that the
+            # device never idles into the timed region; then the K steps as nrep replays of the glen-step graph (+ the tail graph), each
+            # between its own pair of events, the inputs restored in front of each outside the pair: the MEDIAN replay is the figure
+            for _ in range(settle_reps):
+                graph.replay()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nrep + (tail > 0))]
+            for r, (a, b) in enumerate(ev):
+                restore_inputs()
+                a.record(side)
+                (graph if r < nrep else tail_graph).replay()
+                b.record(side)
+            torch.cuda.synchronize()
+            replay_ms = [a.elapsed_time(b) for a, b in ev[:nrep]]
+            tail_ms = ev[-1][0].elapsed_time(ev[-1][1]) if tail else None
+            region_ms = ev[0][0].elapsed_time(ev[-1][1])
+            elapsed = median(replay_ms) * 1e-3 / glen * steps   # seconds for the K steps at the median replay's rate
         else:
+            t0 = time.perf_counter()
             e0.record(side)
             for i in range(steps):
-                one_step(i)
+                y_last = one_step(i)
             e1.record(side)
             torch.cuda.synchronize()
             host_elapsed = time.perf_counter() - t0
             elapsed = e0.elapsed_time(e1) * 1e-3                # seconds between the two events on the launch stream
+            region_ms = elapsed * 1e3
         barrier(world, device)
-        # the previous rounds' figure, kept beside the median: ONE replay between two events, from a synchronised (idle) stream
+        if args.dump_outputs and rank == 0:                     # what the timed path handed its caller in the last timed step
+            dump_outputs(args.dump_outputs, output_sample(y_last))
+        # --full: the previous rounds' figure, ONE replay between two events, from a synchronised (idle) stream
         single_ms = None
-        if graph is not None:
+        if graph is not None and args.full:
             restore_inputs()
             torch.cuda.synchronize()
             e0.record(side)
@@ -509,28 +567,30 @@ def main(argv=None):
             torch.cuda.synchronize()
             single_ms = e0.elapsed_time(e1)
 
-        # ---- dominant kernel (the int8 MFMA GEMM + fused epilogue) alone, HIP events on the launch stream ------------
-        ind_buf, n_dev = layer._ind_dev()
-        q_x, x_out = mixlib.QuantFused(base.clone(), ind_buf, cache.x_scale, bit, SIGMA, n_dev=n_dev, fmt=layer.x_fmt())
-        cache.q_xcache, cache.activation_outliers, cache.n_dev = q_x, (x_out[:, :n_ind] if n_ind else None), n_dev
-        gsteps = max(20, min(steps, 200))
-        for _ in range(5):
-            layer._gemm(cache, rows, 0)
-        torch.cuda.synchronize()
-        gg = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(gg, stream=side):
-            for _ in range(gsteps):
+        # ---- --full: dominant kernel (the int8 MFMA GEMM + fused epilogue) alone, HIP events on the launch stream
+        gemm_us = None
+        if args.full:
+            ind_buf, n_dev = layer._ind_dev()
+            q_x, x_out = mixlib.QuantFused(base.clone(), ind_buf, cache.x_scale, bit, SIGMA, n_dev=n_dev, fmt=layer.x_fmt())
+            cache.q_xcache, cache.activation_outliers, cache.n_dev = q_x, (x_out[:, :n_ind] if n_ind else None), n_dev
+            gsteps = max(20, min(steps, 200))
+            for _ in range(5):
                 layer._gemm(cache, rows, 0)
-        torch.cuda.synchronize()
-        gemm_ms, gemm_first_ms, _ = conditioned_replay(gg, side, settle_ms=0.0 if args.no_graph else None)   # the same clock conditioning as for the step
-        gemm_us = gemm_ms * 1e3 / gsteps
+            torch.cuda.synchronize()
+            gg = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gg, stream=side):
+                for _ in range(gsteps):
+                    layer._gemm(cache, rows, 0)
+            torch.cuda.synchronize()
+            gemm_ms, gemm_first_ms, _ = conditioned_replay(gg, side, settle_ms=0.0 if args.no_graph else None)   # the same clock conditioning as for the step
+            gemm_us = gemm_ms * 1e3 / gsteps
 
-        # ---- secondary timings, outside the timed region of `value` --------------------------------------
+        # ---- --full: secondary timings, outside the timed region of `value` -------------------------------
         eager_ms = cold_ms = None
         cold_note = None
         mlp_ms = {}
         secondary = {}
-        if not args.no_secondary and rank == 0:                 # (rank 0 only: the other ranks wait for it in the counter gather)
+        if args.full and not args.no_secondary and rank == 0:   # (rank 0 only: the other ranks wait for it in the counter gather)
             # (a) the reference's own protocol, examples/benchbitsand.py:534-550: NO graph, 10 warm-up + 100 timed back-to-back
             # `layer(x)` calls from Python between two events - what a plain Hugging Face loop pays per layer, host cost included
             esteps = 100
@@ -622,18 +682,13 @@ def main(argv=None):
 
     flops_step = 2.0 * rows * N * K
     max_elapsed, total_flops, per_rank = gather_counters(elapsed, flops_step * steps, world, device, per_rank=True)
-    max_host, _ = gather_counters(host_elapsed, 0.0, world, device)
+    max_host = None if graph is not None else gather_counters(host_elapsed, 0.0, world, device)[0]
     value = total_flops / max_elapsed / 1e12
     ms_per_step = max_elapsed * 1e3 / steps
     dist_info = describe_group(world, device, args.backend)
-    achieved = flops_step / (gemm_us * 1e-6) / 1e12
 
     if rank == 0:
         fmt = layer.x_fmt()
-        # (the committed PMC passes profiled the metric configuration: any other shape / bit width / per-rank batch carries no traffic figure)
-        ttag = {(8, 512, 4096, 11008): "", (4, 512, 4096, 11008): "_w4a4", (8, 512, 8192, 28672): "_8192x28672"}.get((bit, rows, K, N))
-        cfg_now = _capi.gemm_config_names()[_capi.load().mixq_gemm_pick_config_fmt(rows, N, K, bit, mixlib.fmt_of(layer._wpk))]
-        traffic, traffic_src = hbm_traffic_from_profile(ttag, cfg_now) if ttag is not None else (None, None)
         shape_note = "Llama-2-7b up_proj shape" if (K, N) == (4096, 11008) else f"{K}->{N}"
         out = {
             "metric": f"effective int8 TFLOPS, W{bit}A{bit}O16 MixQ Linear forward (quantise + {'int8' if bit == 8 or fmt != 4 else 'FP6-pipe'} MFMA GEMM + fused dequant/outlier "
@@ -647,52 +702,65 @@ def main(argv=None):
                        "weights": "nn.Linear default init, quantised per output channel", "per_gpu_batch": rows,
                        "parallelism": f"batch-shard x{world} ({'independent replicas' if args.scaling == 'weak' else 'rows of one batch split'}, "
                                       f"no data-path collective)",
-                       "launch": "eager" if args.no_graph else f"one hipGraph of {steps} steps",
+                       "launch": "eager" if args.no_graph else f"{nrep} replays of one hipGraph of {glen} steps" + (f" + one of {tail} steps" if tail else ""),
                        "operand_format": {"activations": {0: "plain", 1: "P16x64", 4: "R6x128 (int4 as FP6 E3M2 codes, row-contiguous)"}[fmt],
                                "weights": {0: "plain", 1: "P16x64", 2: "F16x64", 3: "F6x128 (int4 as FP6 E3M2 codes)"}[mixlib.fmt_of(layer._wpk)]},
                        "weight_bytes_resident": int(layer._wpk.numel() + (0 if layer._buffers['q_weight'] is None else layer._buffers['q_weight'].numel()))},
             "timing": {"clock": "HIP events on the launch stream around the K steps" if graph is None else
-                                f"HIP events on the launch stream around each of {args.replays} back-to-back replays of the K-step graph (inputs restored "
-                                f"between replays, outside the event pairs); ms_per_step = MEDIAN replay / K",
+                                f"HIP events on the launch stream around each of {nrep} back-to-back replays of a {glen}-step graph"
+                                + (f" and one replay of a {tail}-step graph" if tail else "") + " (inputs restored in front of every replay, outside the "
+                                f"event pairs): the K = {steps} timed steps; ms_per_step = MEDIAN {glen}-step replay / {glen}",
+                       "steps_per_graph": None if graph is None else glen,
                        "replays": None if replay_ms is None else len(replay_ms),
                        "replay_ms_min": None if replay_ms is None else round(min(replay_ms), 5),
                        "replay_ms_median": None if replay_ms is None else round(median(replay_ms), 5),
                        "replay_ms_mean": None if replay_ms is None else round(sum(replay_ms) / len(replay_ms), 5),
                        "replay_ms_max": None if replay_ms is None else round(max(replay_ms), 5),
-                       "single_replay_ms_per_step": None if single_ms is None else round(single_ms / steps, 5),
-                       "single_replay_protocol": "ONE replay between two events from a synchronised stream (rounds 1-4's figure; carries the graph-launch latency)",
-                       "host_wall_ms_per_step": round(max_host * 1e3 / steps, 5),
+                       "tail_replay_ms": None if tail_ms is None else round(tail_ms, 5),
+                       "timed_region_ms": round(region_ms, 5),
+                       "host_wall_ms_per_step": None if max_host is None else round(max_host * 1e3 / steps, 5),
                        "per_rank_ms_per_step": [round(v * 1e3 / steps, 5) for v in per_rank],
-                       "clock_settle": None if graph is None else f"{settle_reps} untimed replays of the captured graph (~{CLOCK_SETTLE_MS:.0f} ms) between the warm-up and the timed region",
-                       "first_replay_ms_per_step": None if first_replay_ms is None else round(first_replay_ms / steps, 5),
-                       "eager_ms_per_step": None if eager_ms is None else round(eager_ms, 5),
-                       "eager_protocol": "no graph: 10 warm-up + 100 back-to-back layer(x) calls from Python between two events (examples/benchbitsand.py:534-550), rank 0",
-                       "cold_weights_ms_per_step": None if cold_ms is None else round(cold_ms, 5), "cold_weights_protocol": cold_note,
-                       "mlp_block_ms": None if True not in mlp_ms else round(mlp_ms[True], 5),
-                       "mlp_block_two_launches_ms": None if False not in mlp_ms else round(mlp_ms[False], 5),
-                       "mlp_block_protocol": "fused RMSNorm + quantise -> gate_proj + up_proj (one launch over interleaved rows | two launches) -> down_proj with the row "
-                                             "maxima from the producer, same batch and shape (hidden -> intermediate -> hidden), graph of 20 blocks, same clock conditioning"},
+                       "clock_settle": None if graph is None else f"{settle_reps} untimed replays of the captured graph (~{CLOCK_SETTLE_MS:.0f} ms) queued "
+                                                                  f"directly in front of the timed replays",
+                       "first_replay_ms_per_step": None if first_replay_ms is None else round(first_replay_ms / glen, 5)},
             "pct_of_int8_mfma_peak": round(100.0 * value / (PEAK_INT8_TOPS * world), 2),
-            # rounds 1-4 reported ONE replay between two events from an idle stream: the same figure of THIS run, for comparison across rounds
-            "ms_per_step_single_replay": None if single_ms is None else round(single_ms / steps, 5),
-            "tflops_single_replay": None if single_ms is None else round(flops_step * world * steps / (single_ms * 1e-3) / 1e12, 2),
-            "secondary_configs": secondary or None,
-            "secondary_protocol": "after the headline's timed region, rank 0, same conditioned_replay protocol: hipGraph of 20 forwards on pristine inputs, "
-                                  "first replay discarded, ~40 ms of untimed replays, median of 15 back-to-back replays; `gemm` = GEMM + fused epilogue alone",
+            "full": args.full,
             "distributed": dist_info,
-            "max_abs_err_vs_dequant_linear": round(max_abs_err, 6),
-            # (W4A4 on the FP6 pipe is priced against the FP6 dense peak, 2x the int8 one: MI355X_MICROARCH.md "Peak FP6/FP4 MFMA ~10 PF dense")
-            "roofline": {"bound": "mfma", "kernel": ("FP6-pipe MFMA GEMM (int4 as E3M2 codes)" if fmt == 4 else "int8 MFMA GEMM") + " + fused epilogue (" +
-                                                    _capi.gemm_config_names()[_capi.load().mixq_gemm_pick_config_fmt(rows, N, K, bit, mixlib.fmt_of(layer._wpk))] + ")",
-                         "rank": 0,
-                         "achieved": round(achieved, 2), "peak": PEAK_INT8_TOPS * (2 if fmt == 4 else 1), "unit": "TFLOP/s",
-                         "frac": round(achieved / (PEAK_INT8_TOPS * (2 if fmt == 4 else 1)), 4), "traffic": traffic, "traffic_source": traffic_src,
-                         "us_per_launch": round(gemm_us, 3), "algorithmic_flops_per_launch": flops_step,
-                         "algorithmic_bytes_per_launch": (rows * K + N * K) * bit // 8 + 2 * rows * N},
             "device": info,
         }
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(rows)
+        if args.full:
+            # (the committed PMC passes profiled the metric configuration: any other shape / bit width / per-rank batch carries no traffic figure)
+            ttag = {(8, 512, 4096, 11008): "", (4, 512, 4096, 11008): "_w4a4", (8, 512, 8192, 28672): "_8192x28672"}.get((bit, rows, K, N))
+            cfg_now = _capi.gemm_config_names()[_capi.load().mixq_gemm_pick_config_fmt(rows, N, K, bit, mixlib.fmt_of(layer._wpk))]
+            traffic, traffic_src = hbm_traffic_from_profile(ttag, cfg_now) if ttag is not None else (None, None)
+            achieved = flops_step / (gemm_us * 1e-6) / 1e12
+            out["timing"].update({
+                "single_replay_ms_per_step": None if single_ms is None else round(single_ms / glen, 5),
+                "single_replay_protocol": "ONE replay between two events from a synchronised stream (rounds 1-4's figure; carries the graph-launch latency)",
+                "eager_ms_per_step": None if eager_ms is None else round(eager_ms, 5),
+                "eager_protocol": "no graph: 10 warm-up + 100 back-to-back layer(x) calls from Python between two events (examples/benchbitsand.py:534-550), rank 0",
+                "cold_weights_ms_per_step": None if cold_ms is None else round(cold_ms, 5), "cold_weights_protocol": cold_note,
+                "mlp_block_ms": None if True not in mlp_ms else round(mlp_ms[True], 5),
+                "mlp_block_two_launches_ms": None if False not in mlp_ms else round(mlp_ms[False], 5),
+                "mlp_block_protocol": "fused RMSNorm + quantise -> gate_proj + up_proj (one launch over interleaved rows | two launches) -> down_proj with the row "
+                                      "maxima from the producer, same batch and shape (hidden -> intermediate -> hidden), graph of 20 blocks, same clock conditioning"})
+            out.update({
+                # rounds 1-4 reported ONE replay between two events from an idle stream: the same figure of THIS run, for comparison across rounds
+                "ms_per_step_single_replay": None if single_ms is None else round(single_ms / glen, 5),
+                "tflops_single_replay": None if single_ms is None else round(flops_step * world * glen / (single_ms * 1e-3) / 1e12, 2),
+                "secondary_configs": secondary or None,
+                "secondary_protocol": "after the headline's timed region, rank 0, same conditioned_replay protocol: hipGraph of 20 forwards on pristine inputs, "
+                                      "first replay discarded, ~40 ms of untimed replays, median of 15 back-to-back replays; `gemm` = GEMM + fused epilogue alone",
+                "max_abs_err_vs_dequant_linear": round(max_abs_err, 6),
+                # (W4A4 on the FP6 pipe is priced against the FP6 dense peak, 2x the int8 one: MI355X_MICROARCH.md "Peak FP6/FP4 MFMA ~10 PF dense")
+                "roofline": {"bound": "mfma", "kernel": ("FP6-pipe MFMA GEMM (int4 as E3M2 codes)" if fmt == 4 else "int8 MFMA GEMM") + f" + fused epilogue ({cfg_now})",
+                             "rank": 0,
+                             "achieved": round(achieved, 2), "peak": PEAK_INT8_TOPS * (2 if fmt == 4 else 1), "unit": "TFLOP/s",
+                             "frac": round(achieved / (PEAK_INT8_TOPS * (2 if fmt == 4 else 1)), 4), "traffic": traffic, "traffic_source": traffic_src,
+                             "us_per_launch": round(gemm_us, 3), "algorithmic_flops_per_launch": flops_step,
+                             "algorithmic_bytes_per_launch": (rows * K + N * K) * bit // 8 + 2 * rows * N}})
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(rows)
         print(json.dumps(out), flush=True)
     if world > 1:
         import torch.distributed as dist

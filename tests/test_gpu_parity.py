@@ -1664,13 +1664,13 @@ def test_packed_operands_behind_the_reference_call_sequence():
 # the bench line's contract (what the driver parses)
 # ---------------------------------------------------------------------------------------------------------------
 def test_bench_line_contract_on_the_gpu():
-    """`python bench.py --steps 20 --warmup 5` prints ONE JSON line with the fields the driver reads: metric / value / unit / n_gpus /
+    """`python bench.py --steps 20 --warmup 5 --full` prints ONE JSON line with the fields the driver reads: metric / value / unit / n_gpus /
     steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload, a `roofline` object for the
     dominant kernel (measured live: achieved = algorithmic flops / its launch time) and a `cpu_baseline` object; value is consistent
     with ms_per_step, and the self-check against the dequantised Linear is inside the 1e-2 gate."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5"], capture_output=True, text=True,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--full"], capture_output=True, text=True,
                        timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

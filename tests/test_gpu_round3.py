@@ -168,7 +168,7 @@ def test_full_size_operator_remaining_shapes_with_one_percent_outliers(K, N):
 # ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("extra,K,N,bit", [(["--shape", "8192,28672"], 8192, 28672, 8), (["--bit", "4"], 4096, 11008, 4)])
 def test_bench_other_configs_run(extra, K, N, bit):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-secondary"] + extra,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-secondary"] + extra,
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -5,11 +5,11 @@
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 cd $R
-for i in 1 2 3; do python3 bench.py --gpus 1 --steps 20 --warmup 5 $( [ $i -gt 1 ] && echo --no-cpu-baseline ) > $O/r05p_bench_line$i.json 2>> $O/r05p_bench.err; done
-python3 bench.py --gpus 1 --steps 20 --warmup 5 --bit 4 --no-cpu-baseline > $O/r05p_bench_line_w4a4.json 2>> $O/r05p_bench.err
+for i in 1 2 3; do python3 bench.py --gpus 1 --steps 20 --warmup 5 --full $( [ $i -gt 1 ] && echo --no-cpu-baseline ) > $O/r05p_bench_line$i.json 2>> $O/r05p_bench.err; done
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --bit 4 --no-cpu-baseline > $O/r05p_bench_line_w4a4.json 2>> $O/r05p_bench.err
 cd /tmp && export TMPDIR=/tmp
 prof() { tag=$1; shift; timeout 500 rocprofv3 "$@" > $O/r05p_$tag.log 2>&1; }
-B="python3 $R/bench.py --gpus 1 --no-cpu-baseline --no-secondary"
+B="python3 $R/bench.py --gpus 1 --full --no-cpu-baseline --no-secondary"
 prof kt --kernel-trace -d $O/prof_r05p_kt -o kt -- $B --steps 20 --warmup 5
 prof kt_k11008 --kernel-trace -d $O/prof_r05p_kt_k11008 -o kt -- $B --steps 20 --warmup 5 --shape 11008,4096
 prof kt_mlp --kernel-trace -d $O/prof_r05p_kt_mlp -o kt -- python3 $R/tools/bench_mlp.py

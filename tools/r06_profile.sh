@@ -4,12 +4,12 @@
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 cd $R
-for i in 1 2 3; do python3 bench.py --gpus 1 --steps 20 --warmup 5 $( [ $i -gt 1 ] && echo --no-cpu-baseline ) > $O/r06p_bench_line$i.json 2>> $O/r06p_bench.err; done
-python3 bench.py --gpus 1 --steps 20 --warmup 5 --bit 4 --no-cpu-baseline > $O/r06p_bench_line_w4a4.json 2>> $O/r06p_bench.err
+for i in 1 2 3; do python3 bench.py --gpus 1 --steps 20 --warmup 5 --full $( [ $i -gt 1 ] && echo --no-cpu-baseline ) > $O/r06p_bench_line$i.json 2>> $O/r06p_bench.err; done
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --bit 4 --no-cpu-baseline > $O/r06p_bench_line_w4a4.json 2>> $O/r06p_bench.err
 MIXQ_TUNING_LIB=1 timeout 300 python3 tools/prefill_sweep.py --bit 4 --tokens 512,2048 --layers 11008x4096,4096x4096 --cfgs wr128x192_s16_d4_l2,wr128x192_f6r_xw1,wr128x192_f6r_xw2,wr128x192_f6r_xw4 --rounds 15 2>&1 | grep -v amdgpu.ids > $O/r06p_f6_xwg.txt
 cd /tmp && export TMPDIR=/tmp
 prof() { tag=$1; shift; timeout 500 rocprofv3 "$@" > $O/r06p_$tag.log 2>&1; }
-B="python3 $R/bench.py --gpus 1 --no-cpu-baseline --no-secondary"
+B="python3 $R/bench.py --gpus 1 --full --no-cpu-baseline --no-secondary"
 prof kt --kernel-trace -d $O/prof_r06p_kt -o kt -- $B --steps 20 --warmup 5
 prof kt_w4a4 --kernel-trace -d $O/prof_r06p_kt_w4a4 -o kt -- $B --steps 20 --warmup 5 --bit 4
 prof fetch --pmc FETCH_SIZE -d $O/prof_r06p_fetch -o pmc -- $B --steps 20 --warmup 2 --no-graph

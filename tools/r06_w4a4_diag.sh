@@ -11,7 +11,7 @@ timeout 300 python3 tools/trace_kstep.py --nout 0 2>&1 | grep -v amdgpu.ids >> $
 timeout 300 python3 tools/trace_gemm.py --f6 --bit 4 --nout 128 --shapes 512x11008x4096 --cfgs wr128x192_s16_d4_l2,wr128x192_f6r_abl3_mfma 2>&1 | grep -v amdgpu.ids > $O/r06d_gemm_trace.txt; cat $O/r06d_gemm_trace.txt
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --list-avail > $O/r06d_avail.txt 2>&1
-B="python3 $R/bench.py --gpus 1 --no-cpu-baseline --no-secondary --bit 4 --steps 20 --warmup 2 --no-graph"
+B="python3 $R/bench.py --gpus 1 --full --no-cpu-baseline --no-secondary --bit 4 --steps 20 --warmup 2 --no-graph"
 prof() { tag=$1; shift; timeout 400 rocprofv3 --pmc "$@" -d $O/prof_r06d_$tag -o pmc -- $B > $O/r06d_$tag.log 2>&1; }
 prof sq SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES GRBM_GUI_ACTIVE
 prof inst SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_INSTS_SALU SQ_INST_CYCLES_VMEM_RD SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM

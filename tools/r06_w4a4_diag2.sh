@@ -19,7 +19,7 @@ prof ta4 4 TA_BUSY_avr TA_TA_BUSY_sum TA_ADDR_STALLED_BY_TC_CYCLES_sum TCP_PENDI
 prof sq8 8 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE
 cd $R
 timeout 900 python3 -X faulthandler -m pytest tests -m gpu -x -q -p no:cacheprovider > $O/r06e_suite.txt 2>&1; echo "suite rc=$?"; grep -v amdgpu.ids $O/r06e_suite.txt | tail -15
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/r06e_bench_line.json 2> $O/r06e_bench.err; echo "bench rc=$?"; tail -3 $O/r06e_bench.err
+timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/r06e_bench_line.json 2> $O/r06e_bench.err; echo "bench rc=$?"; tail -3 $O/r06e_bench.err
 python3 - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r06e_bench_line.json').read().strip().splitlines()[-1])
