@@ -102,6 +102,18 @@ int mixq_version(void);
 /* Writes up to `cap` bytes of a NUL-terminated description ("gfx950 cu=256 ...") ; returns MIXQ_ENODEV without GPU. */
 int mixq_device_info(char* buf_host, int cap);
 
+/* ---- bfloat16 activations (ABI 1.1) ---------------------------------------------------------------------------------------
+ * Every entry point with a `_bf16` suffix takes exactly the arguments of its fp16 twin; the 16-bit ACTIVATION pointers (x, x_out) then
+ * hold bfloat16 (uint16_t storage, the top half of an IEEE binary32).  x_scale stays fp16 in every form: a model's cache holds one
+ * x_scale buffer for all of its layers.  The conventions are the fp16 ones with the container swapped:
+ *   x_scale[m] = fp16( max_k |x[m,k]| / qmax )   over the non-outlier columns of the bf16 row (fp32 divide, RNE to fp16)
+ *   q[m,k]     = clamp( rint_half_even( float(x[m,k]) / float(x_scale[m]) ), -qmax, qmax ); all-zero row -> 0
+ * (the division-free quantiser is checked against this form for every finite bf16 x and every finite fp16 s > 0:
+ * mixq_selftest_quant_exact_bf16).  A row whose inlier maximum exceeds 65504 * qmax has no finite fp16 scale: outside the supported
+ * range.  The outlier columns (x_out) carry the bf16 values unchanged, whatever their magnitude.  Outlier detection flags
+ * |x| > fp16(sigma) as for fp16.  Defined for: mixq_find_row_scale, mixq_extract_outliers_zero, mixq_quant_fused(_masked),
+ * mixq_quant_known_amax (row_amax then holds maxima of bf16 bit patterns), mixq_detect_outlier_cols, mixq_selftest_quant_exact. */
+
 /* ---- (i) per-token absmax + quantise ------------------------------------------------------------------
  * Replaces mixlib.FindRowScale(x, x_scale, M, K, bit) -> q_x   (linear.py:190-193, :221).
  *   x        fp16 [M,K] row-major, ldx elements between rows (read only); values must be finite (the result for
@@ -113,6 +125,8 @@ int mixq_device_info(char* buf_host, int cap);
  */
 int mixq_find_row_scale(const uint16_t* x, uint16_t* x_scale, void* q,
                         int M, int K, int ldx, int bit, int qfmt, mixq_stream_t stream);
+int mixq_find_row_scale_bf16(const uint16_t* x, uint16_t* x_scale, void* q,
+                             int M, int K, int ldx, int bit, int qfmt, mixq_stream_t stream);
 
 /* ---- outlier extraction -------------------------------------------------------------------------------
  * Replaces mixlib.ExtractOutliersAndSetToZeros(ind, x) -> x_out   (linear.py:189, :205).
@@ -122,6 +136,8 @@ int mixq_find_row_scale(const uint16_t* x, uint16_t* x_scale, void* q,
  */
 int mixq_extract_outliers_zero(uint16_t* x, const int32_t* ind, int n, uint16_t* x_out,
                                int M, int K, int ldx, int ldo, mixq_stream_t stream);
+int mixq_extract_outliers_zero_bf16(uint16_t* x, const int32_t* ind, int n, uint16_t* x_out,
+                                    int M, int K, int ldx, int ldo, mixq_stream_t stream);
 
 /* ---- (i)+(ii) fused: extract + zero + absmax + quantise + misprediction flag, one pass over X ---------
  * Replaces the k2+k1 pair of linear.py:187-193 and the device-side part of the check linear.py:201.
@@ -134,6 +150,9 @@ int mixq_extract_outliers_zero(uint16_t* x, const int32_t* ind, int n, uint16_t*
 int mixq_quant_fused(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev,
                      uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag,
                      int M, int K, int ldx, int ldo, int bit, float sigma, int qfmt, mixq_stream_t stream);
+int mixq_quant_fused_bf16(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev,
+                          uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag,
+                          int M, int K, int ldx, int ldo, int bit, float sigma, int qfmt, mixq_stream_t stream);
 /* The same pass for a caller that KEEPS an OUTLIER MAP of its columns in device memory (a layer whose prediction is frozen: `ind` never
  * changes again).  col_mask = int32 words:
  *     [W = ceil(K / 32) little-endian words : bit c set <=> column c is one of ind[0 .. live count)]
@@ -156,6 +175,9 @@ int mixq_kept_map_words(int K);
 int mixq_quant_fused_masked(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev, const uint32_t* col_mask, int map_words,
                             uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag,
                             int M, int K, int ldx, int ldo, int bit, float sigma, int qfmt, mixq_stream_t stream);
+int mixq_quant_fused_masked_bf16(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev, const uint32_t* col_mask, int map_words,
+                                 uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag,
+                                 int M, int K, int ldx, int ldo, int bit, float sigma, int qfmt, mixq_stream_t stream);
 
 /* ---- online outlier-column detection ------------------------------------------------------------------
  * Replaces torch.unique(torch.where(abs(X) > sigma)[1]).int32  (linear.py:157-161, FindOutliers).
@@ -165,6 +187,8 @@ int mixq_quant_fused_masked(uint16_t* x, const int32_t* ind, int n, const int32_
  */
 int mixq_detect_outlier_cols(const uint16_t* x, float sigma, uint8_t* colflags, int32_t* ind_out,
                              int32_t* count, int M, int K, int ldx, mixq_stream_t stream);
+int mixq_detect_outlier_cols_bf16(const uint16_t* x, float sigma, uint8_t* colflags, int32_t* ind_out,
+                                  int32_t* count, int M, int K, int ldx, mixq_stream_t stream);
 
 /* ---- weight-column dequantisation for newly found outliers --------------------------------------------
  * Replaces `q_weight[:,ind].to(fp16) * scale_col.T` (linear.py:207,305) and, for bit=4,
@@ -225,6 +249,9 @@ int mixq_gemm_amax_supported(int M, int N, int K, int layout);
 int mixq_quant_known_amax(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev, uint32_t* row_amax,
                           const uint32_t* col_mask, int map_words, uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag,
                           int M, int K, int ldx, int ldo, int bit, float sigma, int qfmt, mixq_stream_t stream);
+int mixq_quant_known_amax_bf16(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev, uint32_t* row_amax,
+                               const uint32_t* col_mask, int map_words, uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag,
+                               int M, int K, int ldx, int ldo, int bit, float sigma, int qfmt, mixq_stream_t stream);
 
 /* ---- the whole forward of a frozen layer in ONE call ---------------------------------------------------------
  * mixq_linear_forward = mixq_quant_fused followed by mixq_gemm_i8_fused / mixq_gemm_i4_fused, both launched from C on `stream`:
@@ -366,6 +393,7 @@ int mixq_gemm_set_fuse_probe(const void* x, void* scratch, void* counters, int K
  * finite fp16 x and all finite fp16 s > 0, ~2e9 pairs, ~1 s): adds the number of disagreements with the IEEE-division form
  * to *mismatches_dev (a zeroed device counter).  bit = 8 or 4. */
 int mixq_selftest_quant_exact(unsigned long long* mismatches_dev, int bit, mixq_stream_t stream);
+int mixq_selftest_quant_exact_bf16(unsigned long long* mismatches_dev, int bit, mixq_stream_t stream);
 int mixq_gemm_num_configs(void);
 int mixq_gemm_config_name(int cfg, char* buf_host, int cap);
 /* The config the automatic choice picks for (M,N,K,bit) with MIXQ_FMT_P16X64 operands / with operands in `fmt`. */

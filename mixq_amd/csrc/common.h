@@ -69,6 +69,15 @@ __device__ __forceinline__ float h2f(uint16_t h) {
 __device__ __forceinline__ uint16_t f2h(float f) {   // round-to-nearest-even
     return __half_as_ushort(__float2half_rn(f));
 }
+// The 16-bit ACTIVATION container of a kernel instantiation: BF = false is IEEE fp16 (h2f above), BF = true bfloat16 (the top half of an
+// fp32: widening is a shift).  Scales (x_scale, scale_col) and bias stay fp16 in either form
+// (include/mixq_hip.h, "bf16 activations").  For finite values of either container |a| < |b| <=> (a & 0x7fff) < (b & 0x7fff) as unsigned,
+// so the bit-pattern maxima of the quantisers and of the amax side output serve both.
+template <bool BF>
+__device__ __forceinline__ float a2f(uint16_t h) {
+    if constexpr (BF) return __uint_as_float(static_cast<uint32_t>(h) << 16);
+    else return h2f(h);
+}
 // Maximum over the 64 lanes of a NON-NEGATIVE value, returned in every lane.  DPP moves inside the 16-lane rows (quad
 // swaps, half mirror, mirror: 4 VALU) and four v_readlane for the rows, instead of six ds_bpermute round trips.
 template <int CTRL>
@@ -89,7 +98,12 @@ __device__ __forceinline__ float wave_max(float v) {
 // x_scale = fp16(amax / qmax) (include/mixq_hip.h: fp32 divide, RNE to fp16) WITHOUT the division: for every finite fp16 maximum and both
 // qmax (127, 7), fp16(RN(amax * RN(1 / qmax))) is the same fp16 value (checked exhaustively: tests/test_oracle_golden.py) - one multiply
 // instead of a ~10-instruction IEEE division on every row's critical path (maximum -> scale -> quantise).
-__device__ __forceinline__ uint16_t mixq_row_scale(float amax, float qmax) { return f2h(amax * (1.0f / qmax)); }
+// A bf16 maximum keeps the division: the product form differs for three bf16 values at qmax = 7 (fp16 subnormal scales).
+template <bool BF = false>
+__device__ __forceinline__ uint16_t mixq_row_scale(float amax, float qmax) {
+    if constexpr (BF) return f2h(__fdiv_rn(amax, qmax));
+    else return f2h(amax * (1.0f / qmax));
+}
 // 1 / s for the per-value products of quant_exact / quant8_exact below: the IEEE division.  (v_rcp_f32, 1 ulp, passes the exhaustive self-test
 // too - the exactness argument below has the slack: t within 3.5e-5 of x / s, needed < 6e-5 - and changed no timing in round 5: not taken.)
 __device__ __forceinline__ float mixq_rcp_scale(float s) { return s > 0.f ? __fdiv_rn(1.0f, s) : 0.f; }
@@ -100,7 +114,8 @@ __device__ __forceinline__ float mixq_rcp_scale(float s) { return s > 0.f ? __fd
 // least 1/(4b) > 6e-5 away from one, while t = x * rs is within 2e-5 of x/s - so rint(t) is the correctly rounded quotient
 // unless x/s is an exact tie; the tie is detected from the exact residual e = x - q0 s (|q0| s has <= 18 significant bits) and
 // resolved to even.  The same argument shows rint(RN(x/s)) == rint_half_even(x/s), i.e. this equals the division form bit
-// for bit.
+// for bit.  A bfloat16 x (8-bit significand) shortens a and changes nothing else: mixq_selftest_quant_exact_bf16 checks every finite bf16 x
+// against every finite fp16 s.
 template <int BIT>
 __device__ __forceinline__ int quant_exact(float x, float s, float rs) {
     constexpr float QMAX = static_cast<float>((1 << (BIT - 1)) - 1);
@@ -123,7 +138,7 @@ __device__ __forceinline__ int quant_exact(float x, float s, float rs) {
 // against the division form over every finite fp16 pair.
 constexpr float MIXQ_RMAGIC = 12582912.f;                                     // 1.5 * 2^23 = 0x4B400000
 __device__ __forceinline__ int quant8_int(uint32_t ubits) { return static_cast<int>(ubits & 0x7fffffu) - 0x400000; }
-template <int BIT>
+template <int BIT, bool BF = false>
 __device__ __forceinline__ void quant8_exact(const uint4& v, float s, float rs, uint32_t (&ub)[8]) {
     constexpr float QMAX = static_cast<float>((1 << (BIT - 1)) - 1);
     const uint32_t w[4] = {v.x, v.y, v.z, v.w};
@@ -132,7 +147,7 @@ __device__ __forceinline__ void quant8_exact(const uint4& v, float s, float rs, 
     bool tie = false;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const float x = h2f(static_cast<uint16_t>((j & 1) ? (w[j >> 1] >> 16) : (w[j >> 1] & 0xffffu)));
+        const float x = a2f<BF>(static_cast<uint16_t>((j & 1) ? (w[j >> 1] >> 16) : (w[j >> 1] & 0xffffu)));
         const float t = __builtin_amdgcn_fmed3f(x * rs, -QMAX, QMAX);
         u[j] = t + MIXQ_RMAGIC;
         e[j] = fmaf(-(u[j] - MIXQ_RMAGIC), s, x);

@@ -1160,7 +1160,7 @@ extern "C" int mixq_gemm_pick_config_fmt(int M, int N, int K, int bit, int fmt) 
     return mixq_gemm_pick_config(M, N, K, bit);
 }
 
-extern "C" int mixq_version(void) { return 1000; }
+extern "C" int mixq_version(void) { return 1001; }   // 1.1: the _bf16 entry points
 
 extern "C" int mixq_device_info(char* buf, int cap) {
     if (!buf || cap <= 0) return MIXQ_EINVAL;

@@ -39,24 +39,26 @@ __device__ __forceinline__ uint32_t amax8_masked(uint4& v, uint32_t m8, uint32_t
     v = make_uint4(w[0], w[1], w[2], w[3]);
     return acc;
 }
+template <bool BF = false>
 __device__ __forceinline__ float amax_finish(uint32_t acc) {
     const uint32_t lo = acc & 0xffffu, hi = acc >> 16;
-    return h2f(static_cast<uint16_t>(lo > hi ? lo : hi));
+    return a2f<BF>(static_cast<uint16_t>(lo > hi ? lo : hi));
 }
 
 // FP6 codes of a chunk's 8 quantised values (MIXQ_FMT_F6X128)
+template <bool BF = false>
 __device__ __forceinline__ void quant_codes8(const uint4& v, float s, float rs, uint32_t* code) {
     uint32_t ub[8];
-    quant8_exact<4>(v, s, rs, ub);
+    quant8_exact<4, BF>(v, s, rs, ub);
 #pragma unroll
     for (int i = 0; i < 8; ++i) code[i] = f6_code_of_int(quant8_int(ub[i]));
 }
 
 // q: plain -> row base pointer, packed (fmt != 0) -> matrix base pointer
-template <int BIT>
+template <int BIT, bool BF = false>
 __device__ __forceinline__ void quant_store8(const uint4& v, float s, float rs, void* q, int chunk, int row, int rows16, int fmt) {
     uint32_t ub[8];
-    quant8_exact<BIT>(v, s, rs, ub);
+    quant8_exact<BIT, BF>(v, s, rs, ub);
     if constexpr (BIT == 8) {
         uint2 o;
         o.x = quant8_pack4(ub[0], ub[1], ub[2], ub[3]);
@@ -81,7 +83,8 @@ __device__ __forceinline__ void quant_store8(const uint4& v, float s, float rs, 
 
 // One workgroup per row.  NCH = number of 16-byte chunks each thread keeps in registers (row <= NCH*256*8
 // elements stays on chip between the two passes); NCH == 0 re-reads the row (L2-resident) for any K.
-template <int BIT, int NCH>
+// BF (every kernel below): x / x_out hold bfloat16 instead of fp16 (common.h a2f); the fp16 instantiations are the code they were.
+template <int BIT, int NCH, bool BF = false>
 __global__ __launch_bounds__(QT) void quant_rows_kernel(
     uint16_t* __restrict__ x, int ldx, const int32_t* __restrict__ ind, int n_cap, const int32_t* __restrict__ n_dev,
     uint16_t* __restrict__ x_scale, void* __restrict__ q, uint16_t* __restrict__ x_out, int ldo,
@@ -154,9 +157,9 @@ __global__ __launch_bounds__(QT) void quant_rows_kernel(
             amax_acc = amax8_masked(v, m8, amax_acc);
         }
     }
-    const float amax = block_max_256(amax_finish(amax_acc), red);
+    const float amax = block_max_256(amax_finish<BF>(amax_acc), red);
     constexpr float QMAX = static_cast<float>((1 << (BIT - 1)) - 1);
-    const uint16_t sh = mixq_row_scale(amax, QMAX);
+    const uint16_t sh = mixq_row_scale<BF>(amax, QMAX);
     const float s = h2f(sh);
     const float rs = mixq_rcp_scale(s);      // one division per row; quant_exact needs none per element
     if (tid == 0) {
@@ -168,14 +171,14 @@ __global__ __launch_bounds__(QT) void quant_rows_kernel(
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
             const int c = tid + i * QT;
-            if (c < nchunk) quant_store8<BIT>(keep[i], s, rs, qrow, c, row, rows16, fmt);
+            if (c < nchunk) quant_store8<BIT, BF>(keep[i], s, rs, qrow, c, row, rows16, fmt);
         }
     } else {
         for (int c = tid; c < nchunk; c += QT) {
             uint4 v = xv[c];
             uint32_t m8 = have_out ? ((smem[c >> 2] >> ((c & 3) * 8)) & 0xffu) : 0u;
             (void)amax8_masked(v, m8, 0u);
-            quant_store8<BIT>(v, s, rs, qrow, c, row, rows16, fmt);
+            quant_store8<BIT, BF>(v, s, rs, qrow, c, row, rows16, fmt);
         }
     }
 }
@@ -185,7 +188,7 @@ __global__ __launch_bounds__(QT) void quant_rows_kernel(
 // memory while the row loads are in flight (no LDS copy of the row, no second pass over it), the column bitmask is built
 // once per workgroup and shared by its RPB rows, and with TPR == 64 a row lives in ONE wave, so the absmax needs no LDS
 // round trip and no barrier at all when the layer has no outlier columns.  Results are bit-identical to the first form.
-template <int BIT, int TPR, int RPB, int NCH, bool KEPT>
+template <int BIT, int TPR, int RPB, int NCH, bool KEPT, bool BF = false>
 // (parameter order: what a thread needs before it can request its row - 12 dwords - comes FIRST: built with -amdgpu-kernarg-preload-count
 // those arrive in SGPRs with the wave, and no scalar load stands in front of the row request; the rest is waited for behind it)
 // KEPT: the caller handed over the layer's kept outlier map (col_mask != nullptr, n_cap > 0) - the instantiation holds only that route (and
@@ -302,7 +305,7 @@ __global__ __launch_bounds__(TPR * RPB) void quant_rows2_kernel(
             }
         }
     }
-    float amax = wave_max(amax_finish(amax_acc));
+    float amax = wave_max(amax_finish<BF>(amax_acc));
     if constexpr (WPR > 1) {
         if ((tid & 63) == 0) red[tid >> 6] = amax;
         __syncthreads();
@@ -311,7 +314,7 @@ __global__ __launch_bounds__(TPR * RPB) void quant_rows2_kernel(
         for (int w = 1; w < WPR; ++w) amax = fmaxf(amax, red[rw * WPR + w]);
     }                                                      // (WPR == 1: the row lives in ONE wave, whose LDS operations are ordered - the image needs no barrier)
     constexpr float QMAX = static_cast<float>((1 << (BIT - 1)) - 1);
-    const uint16_t sh = mixq_row_scale(amax, QMAX);
+    const uint16_t sh = mixq_row_scale<BF>(amax, QMAX);
     const float s = h2f(sh);
     const float rs = mixq_rcp_scale(s);
     if (!valid) return;
@@ -339,8 +342,8 @@ __global__ __launch_bounds__(TPR * RPB) void quant_rows2_kernel(
                 const int c = chunk(i);
                 if (c < nchunk) {
                     uint32_t code[16];
-                    quant_codes8(keep[i], s, rs, code);
-                    quant_codes8(keep[i + 1], s, rs, code + 8);
+                    quant_codes8<BF>(keep[i], s, rs, code);
+                    quant_codes8<BF>(keep[i + 1], s, rs, code + 8);
                     const int k = c * 8;
 #ifdef MIXQ_TUNING
                     if (dbg & 16) {                                  // timing probe (tools build): the same bytes to a row-contiguous place
@@ -363,7 +366,7 @@ __global__ __launch_bounds__(TPR * RPB) void quant_rows2_kernel(
             const int c = t;
             const bool in = c < nchunk;                                // (K % 128 == 0: both chunks of a pair are in, or neither)
             uint32_t lo = 0, hi = 0;
-            if (in) { uint32_t code[8]; quant_codes8(keep[0], s, rs, code); f6_pack8(code, lo, hi); }
+            if (in) { uint32_t code[8]; quant_codes8<BF>(keep[0], s, rs, code); f6_pack8(code, lo, hi); }
             const uint32_t plo = __shfl_xor(lo, 1), phi = __shfl_xor(hi, 1);
             if (in && !(c & 1)) {
                 const int k = c * 8;
@@ -386,7 +389,7 @@ __global__ __launch_bounds__(TPR * RPB) void quant_rows2_kernel(
                 continue;
             }
 #endif
-            if (c < nchunk) quant_store8<BIT>(keep[i], s, rs, qrow, c, row, rows16, fmt);
+            if (c < nchunk) quant_store8<BIT, BF>(keep[i], s, rs, qrow, c, row, rows16, fmt);
         }
     }
     if constexpr (KEPT) return;                                     // (x_out left in front of the quantise arithmetic)
@@ -412,7 +415,7 @@ __global__ __launch_bounds__(TPR * RPB) void quant_rows2_kernel(
 // patterns maximised with atomics - mixq_gemm_i8_fused_amax): no reduction, no column-mask build (col_mask is the layer's kept outlier
 // map, whose bit words the producer used), one barrier that only orders "everybody has read the maximum" before it is cleared for the next forward.
 // Same bytes out as quant_rows2_kernel on the same row: the scale is fp16(amax / qmax) either way.
-template <int BIT, int TPR, int NCH>
+template <int BIT, int TPR, int NCH, bool BF = false>
 __global__ __launch_bounds__(TPR) void quant_known_kernel(       // (parameter order: see quant_rows2_kernel)
     uint16_t* __restrict__ x, const uint32_t* __restrict__ col_mask, uint32_t* __restrict__ row_amax, const int32_t* __restrict__ n_dev,
     const int32_t* __restrict__ ind, int ldx, int K, int n_cap, int ldo,
@@ -457,7 +460,7 @@ __global__ __launch_bounds__(TPR) void quant_known_kernel(       // (parameter o
     __syncthreads();                                                      // every thread of the row has read the maximum (and dropped its outlier values into LDS) ...
     if (t == 0) row_amax[row] = 0u;                                       // ... before it is cleared for the producer's next run
     constexpr float QMAX = static_cast<float>((1 << (BIT - 1)) - 1);
-    const uint16_t sh = mixq_row_scale(h2f(static_cast<uint16_t>(abits)), QMAX);
+    const uint16_t sh = mixq_row_scale<BF>(a2f<BF>(static_cast<uint16_t>(abits)), QMAX);
     const float s = h2f(sh);
     const float rs = mixq_rcp_scale(s);
     if (t == 0) {
@@ -473,7 +476,7 @@ __global__ __launch_bounds__(TPR) void quant_known_kernel(       // (parameter o
         if (c < nchunk) {
             // (without a usable map: zero the outlier columns of the chunk, whatever the load saw there, from the map's bit words)
             if (!kept && col_mask) (void)amax8_masked(keep[i], (col_mask[c >> 2] >> ((c & 3) * 8)) & 0xffu, 0u);
-            quant_store8<BIT>(keep[i], s, rs, qrow, c, row, rows16, fmt);
+            quant_store8<BIT, BF>(keep[i], s, rs, qrow, c, row, rows16, fmt);
         }
     }
     if (kept) return;                                                     // (x_out left in front of the quantise arithmetic)
@@ -510,6 +513,7 @@ __global__ __launch_bounds__(QT) void extract_kernel(uint16_t* __restrict__ x, i
 
 // Column-wise OR of |x| > thr over a slab of rows; 8 columns (16 bytes) per thread.
 constexpr int DET_ROWS = 16;
+template <bool BF = false>
 __global__ __launch_bounds__(QT) void detect_cols_kernel(const uint16_t* __restrict__ x, int ldx, int M, int K,
                                                          float thr, uint8_t* __restrict__ colflags)
 {
@@ -523,8 +527,8 @@ __global__ __launch_bounds__(QT) void detect_cols_kernel(const uint16_t* __restr
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            if (fabsf(h2f(static_cast<uint16_t>(w[i] & 0xffffu))) > thr) hit |= 1u << (2 * i);
-            if (fabsf(h2f(static_cast<uint16_t>(w[i] >> 16))) > thr)     hit |= 1u << (2 * i + 1);
+            if (fabsf(a2f<BF>(static_cast<uint16_t>(w[i] & 0xffffu))) > thr) hit |= 1u << (2 * i);
+            if (fabsf(a2f<BF>(static_cast<uint16_t>(w[i] >> 16))) > thr)     hit |= 1u << (2 * i + 1);
         }
     }
     if (hit) {
@@ -663,7 +667,7 @@ constexpr int g_quant_dbg = 0;
 #endif
 constexpr int NUM_QUANT_CFGS = 10;
 
-template <int BIT, int TPR, int RPB>
+template <int BIT, int TPR, int RPB, bool BF>
 int launch_quant_rows2(uint16_t* x, int ldx, const int32_t* ind, int n, const int32_t* n_dev, uint16_t* x_scale, void* q,
                        uint16_t* x_out, int ldo, int32_t* flag, int M, int K, float thr_scale, int qfmt, hipStream_t st,
                        const uint32_t* col_mask)
@@ -675,7 +679,7 @@ int launch_quant_rows2(uint16_t* x, int ldx, const int32_t* ind, int n, const in
                                 : (static_cast<size_t>((K + 31) >> 5) + RPB * (TPR / 64)) * sizeof(uint32_t);
     const int rows16 = qfmt ? ((M + 15) & ~15) : 0;
     dim3 g((M + RPB - 1) / RPB), b(TPR * RPB);
-#define MIXQ_QLAUNCH2K(NCH, KEPT) hipLaunchKernelGGL((quant_rows2_kernel<BIT, TPR, RPB, NCH, KEPT>), g, b, shm, st, x, col_mask, n_dev, ind, ldx, M, K, n, x_scale, q, x_out, ldo, flag, thr_scale, rows16, qfmt, g_quant_dbg)
+#define MIXQ_QLAUNCH2K(NCH, KEPT) hipLaunchKernelGGL((quant_rows2_kernel<BIT, TPR, RPB, NCH, KEPT, BF>), g, b, shm, st, x, col_mask, n_dev, ind, ldx, M, K, n, x_scale, q, x_out, ldo, flag, thr_scale, rows16, qfmt, g_quant_dbg)
 #define MIXQ_QLAUNCH2(NCH) do { if (col_mask) MIXQ_QLAUNCH2K(NCH, true); else MIXQ_QLAUNCH2K(NCH, false); } while (0)
     if      (nchunk <= 1 * TPR)  MIXQ_QLAUNCH2(1);
     else if (nchunk <= 2 * TPR)  MIXQ_QLAUNCH2(2);
@@ -689,7 +693,7 @@ int launch_quant_rows2(uint16_t* x, int ldx, const int32_t* ind, int n, const in
     return mixq_launch_status();
 }
 
-template <int BIT>
+template <int BIT, bool BF = false>
 int launch_quant_rows(uint16_t* x, int ldx, const int32_t* ind, int n, const int32_t* n_dev, uint16_t* x_scale, void* q,
                       uint16_t* x_out, int ldo, int32_t* flag, int M, int K, float thr_scale, int qfmt, hipStream_t st,
                       const uint32_t* col_mask = nullptr)      // (optional: the kept outlier map of `ind`; the round-1 kernel builds its own mask)
@@ -706,13 +710,16 @@ int launch_quant_rows(uint16_t* x, int ldx, const int32_t* ind, int n, const int
         // (256,2) 6.31 | (512,1) 6.25 | (512,2) 6.11 us, at 11008 (512,x) 11.2-11.3 | (256,x) 12.2-12.3 (profiles/r03_w4a4_quant_formats.txt)
         if (qfmt == MIXQ_FMT_F6X128 || qfmt == MIXQ_FMT_R6X128) cfg = nchunk <= 256 ? 5 : (qfmt == MIXQ_FMT_F6X128 && nchunk <= 512 ? 7 : 9);
     }
+    // bf16 is instantiated only for the geometries the choice above returns (5 .. 9) and the any-K fallback behind them: a forced
+    // test geometry 0 .. 4 (mixq_quant_set_config) has no bf16 form
+    if (BF && cfg < 5) return MIXQ_EINVAL;
     int rc = -100;
-#define MIXQ_Q2(TPR, RPB) rc = launch_quant_rows2<BIT, TPR, RPB>(x, ldx, ind, n, n_dev, x_scale, q, x_out, ldo, flag, M, K, thr_scale, qfmt, st, col_mask)
+#define MIXQ_Q2(TPR, RPB) rc = launch_quant_rows2<BIT, TPR, RPB, BF>(x, ldx, ind, n, n_dev, x_scale, q, x_out, ldo, flag, M, K, thr_scale, qfmt, st, col_mask)
     switch (cfg) {
-        case 1: MIXQ_Q2(64, 1); break;
-        case 2: MIXQ_Q2(64, 2); break;
-        case 3: MIXQ_Q2(64, 4); break;
-        case 4: MIXQ_Q2(128, 1); break;
+        case 1: if constexpr (!BF) MIXQ_Q2(64, 1); break;
+        case 2: if constexpr (!BF) MIXQ_Q2(64, 2); break;
+        case 3: if constexpr (!BF) MIXQ_Q2(64, 4); break;
+        case 4: if constexpr (!BF) MIXQ_Q2(128, 1); break;
         case 5: MIXQ_Q2(128, 2); break;
         case 6: MIXQ_Q2(256, 1); break;
         case 7: MIXQ_Q2(256, 2); break;
@@ -728,8 +735,10 @@ int launch_quant_rows(uint16_t* x, int ldx, const int32_t* ind, int n, const int
                        + (nchunk <= 8 * QT ? static_cast<size_t>(K) * 2 : 0);
     const int rows16 = qfmt ? ((M + 15) & ~15) : 0;
     dim3 g(M), b(QT);
-#define MIXQ_QLAUNCH(NCH) hipLaunchKernelGGL((quant_rows_kernel<BIT, NCH>), g, b, shm, st, x, ldx, ind, n, n_dev, x_scale, q, x_out, ldo, flag, K, thr_scale, rows16, qfmt)
-    if      (nchunk <= 2 * QT)  MIXQ_QLAUNCH(2);
+#define MIXQ_QLAUNCH(NCH) hipLaunchKernelGGL((quant_rows_kernel<BIT, NCH, BF>), g, b, shm, st, x, ldx, ind, n, n_dev, x_scale, q, x_out, ldo, flag, K, thr_scale, rows16, qfmt)
+    // (bf16 reaches this kernel only behind geometries 5 .. 9, i.e. for rows of more than 16 x 256 chunks: the any-K form)
+    if constexpr (BF)           MIXQ_QLAUNCH(0);
+    else if (nchunk <= 2 * QT)  MIXQ_QLAUNCH(2);
     else if (nchunk <= 4 * QT)  MIXQ_QLAUNCH(4);
     else if (nchunk <= 8 * QT)  MIXQ_QLAUNCH(8);
     else if (nchunk <= 16 * QT) MIXQ_QLAUNCH(16);
@@ -746,27 +755,29 @@ inline float fp16_round(float v) {                    // host: value of fp16(v) 
 
 // Self-test of quant_exact (common.h): every finite fp16 x against every finite fp16 scale s > 0, compared with the
 // division form rint(RN(x / s)) it replaces.  One workgroup per scale value; *mismatches receives the count.
-template <int BIT>
+// BF: every finite bfloat16 x instead (the bf16 quantise passes use the same quotient with a bf16 numerator).
+template <int BIT, bool BF = false>
 __global__ __launch_bounds__(256) void selftest_quant_exact_kernel(unsigned long long* __restrict__ mismatches)
 {
+    const uint32_t INF = BF ? 0x7f80u : 0x7c00u;                          // exponent field all ones: inf / nan
     constexpr float QMAX = static_cast<float>((1 << (BIT - 1)) - 1);
     const float s = h2f(static_cast<uint16_t>(blockIdx.x + 1));          // bits 0x0001 .. 0x7bff
     const float rs = mixq_rcp_scale(s);
     unsigned long long bad = 0;
     for (unsigned xb = threadIdx.x; xb < 65536u; xb += 256) {
-        if ((xb & 0x7c00u) == 0x7c00u) continue;                          // inf / nan
-        const float x = h2f(static_cast<uint16_t>(xb));
+        if ((xb & INF) == INF) continue;                                  // inf / nan
+        const float x = a2f<BF>(static_cast<uint16_t>(xb));
         float q = rintf(__fdiv_rn(x, s));
         q = fminf(fmaxf(q, -QMAX), QMAX);
         bad += quant_exact<BIT>(x, s, rs) != static_cast<int>(q);
         // the chunk form (quant8_exact): this value in slot xb % 8 of a chunk whose other slots hold its neighbours' bit patterns (finite ones)
         uint32_t hw[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { const unsigned o = (xb + 8191u * (j + 1)) & 0xffffu; hw[j] = (o & 0x7c00u) == 0x7c00u ? 0u : o; }
+        for (int j = 0; j < 8; ++j) { const unsigned o = (xb + 8191u * (j + 1)) & 0xffffu; hw[j] = (o & INF) == INF ? 0u : o; }
         hw[xb & 7u] = xb;
         const uint4 v = make_uint4(hw[0] | (hw[1] << 16), hw[2] | (hw[3] << 16), hw[4] | (hw[5] << 16), hw[6] | (hw[7] << 16));
         uint32_t ub[8];
-        quant8_exact<BIT>(v, s, rs, ub);
+        quant8_exact<BIT, BF>(v, s, rs, ub);
         uint32_t got = 0;
 #pragma unroll
         for (int j = 0; j < 8; ++j) if ((xb & 7u) == static_cast<unsigned>(j)) got = ub[j];
@@ -783,9 +794,17 @@ extern "C" int mixq_selftest_quant_exact(unsigned long long* mismatches_dev, int
     else          hipLaunchKernelGGL(selftest_quant_exact_kernel<4>, dim3(0x7bff), dim3(256), 0, mixq_stream(stream), mismatches_dev);
     return mixq_launch_status();
 }
+extern "C" int mixq_selftest_quant_exact_bf16(unsigned long long* mismatches_dev, int bit, mixq_stream_t stream)
+{
+    if (!mismatches_dev || (bit != 8 && bit != 4)) return MIXQ_EINVAL;
+    if (bit == 8) hipLaunchKernelGGL((selftest_quant_exact_kernel<8, true>), dim3(0x7bff), dim3(256), 0, mixq_stream(stream), mismatches_dev);
+    else          hipLaunchKernelGGL((selftest_quant_exact_kernel<4, true>), dim3(0x7bff), dim3(256), 0, mixq_stream(stream), mismatches_dev);
+    return mixq_launch_status();
+}
 
-extern "C" int mixq_find_row_scale(const uint16_t* x, uint16_t* x_scale, void* q, int M, int K, int ldx, int bit, int qfmt,
-                                   mixq_stream_t stream)
+template <bool BF>
+static int find_row_scale_common(const uint16_t* x, uint16_t* x_scale, void* q, int M, int K, int ldx, int bit, int qfmt,
+                                 mixq_stream_t stream)
 {
     if (qfmt != MIXQ_FMT_PLAIN && qfmt != MIXQ_FMT_P16X64 && qfmt != MIXQ_FMT_F16X64 && !((qfmt == MIXQ_FMT_F6X128 || qfmt == MIXQ_FMT_R6X128) && bit == 4)) return MIXQ_EINVAL;
     if (qfmt != MIXQ_FMT_PLAIN && (bit == 8 ? K : K / 2) % 64) return MIXQ_ESHAPE;
@@ -794,10 +813,21 @@ extern "C" int mixq_find_row_scale(const uint16_t* x, uint16_t* x_scale, void* q
     if ((K & 7) || (ldx & 7) || ldx < K || (bit == 4 && (K & 15))) return MIXQ_ESHAPE;
     if (M == 0) return MIXQ_OK;
     uint16_t* xm = const_cast<uint16_t*>(x);           // not written: n = 0 and x_out = NULL
-    if (bit == 8) return launch_quant_rows<8>(xm, ldx, nullptr, 0, nullptr, x_scale, q, nullptr, 0, nullptr, M, K, 0.f, qfmt, mixq_stream(stream));
-    return launch_quant_rows<4>(xm, ldx, nullptr, 0, nullptr, x_scale, q, nullptr, 0, nullptr, M, K, 0.f, qfmt, mixq_stream(stream));
+    if (bit == 8) return launch_quant_rows<8, BF>(xm, ldx, nullptr, 0, nullptr, x_scale, q, nullptr, 0, nullptr, M, K, 0.f, qfmt, mixq_stream(stream));
+    return launch_quant_rows<4, BF>(xm, ldx, nullptr, 0, nullptr, x_scale, q, nullptr, 0, nullptr, M, K, 0.f, qfmt, mixq_stream(stream));
+}
+extern "C" int mixq_find_row_scale(const uint16_t* x, uint16_t* x_scale, void* q, int M, int K, int ldx, int bit, int qfmt,
+                                   mixq_stream_t stream)
+{
+    return find_row_scale_common<false>(x, x_scale, q, M, K, ldx, bit, qfmt, stream);
+}
+extern "C" int mixq_find_row_scale_bf16(const uint16_t* x, uint16_t* x_scale, void* q, int M, int K, int ldx, int bit, int qfmt,
+                                        mixq_stream_t stream)
+{
+    return find_row_scale_common<true>(x, x_scale, q, M, K, ldx, bit, qfmt, stream);
 }
 
+template <bool BF>
 static int quant_fused_common(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev, const uint32_t* col_mask, uint16_t* x_scale, void* q,
                               uint16_t* x_out, int32_t* flag, int M, int K, int ldx, int ldo, int bit, float sigma, int qfmt,
                               mixq_stream_t stream)
@@ -814,15 +844,21 @@ static int quant_fused_common(uint16_t* x, const int32_t* ind, int n, const int3
     const float thr = fp16_round(fp16_round(sigma) / qmax);
     uint16_t* xo = (n > 0) ? x_out : nullptr;
     if (K > 32768) col_mask = nullptr;                 // (the kept route keeps an fp16 image of the row in LDS: beyond 64 KB per row, the in-kernel mask)
-    if (bit == 8) return launch_quant_rows<8>(x, ldx, ind, n, n_dev, x_scale, q, xo, ldo, flag, M, K, thr, qfmt, mixq_stream(stream), col_mask);
-    return launch_quant_rows<4>(x, ldx, ind, n, n_dev, x_scale, q, xo, ldo, flag, M, K, thr, qfmt, mixq_stream(stream), col_mask);
+    if (bit == 8) return launch_quant_rows<8, BF>(x, ldx, ind, n, n_dev, x_scale, q, xo, ldo, flag, M, K, thr, qfmt, mixq_stream(stream), col_mask);
+    return launch_quant_rows<4, BF>(x, ldx, ind, n, n_dev, x_scale, q, xo, ldo, flag, M, K, thr, qfmt, mixq_stream(stream), col_mask);
 }
 
 extern "C" int mixq_quant_fused(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev, uint16_t* x_scale, void* q,
                                 uint16_t* x_out, int32_t* flag, int M, int K, int ldx, int ldo, int bit, float sigma, int qfmt,
                                 mixq_stream_t stream)
 {
-    return quant_fused_common(x, ind, n, n_dev, nullptr, x_scale, q, x_out, flag, M, K, ldx, ldo, bit, sigma, qfmt, stream);
+    return quant_fused_common<false>(x, ind, n, n_dev, nullptr, x_scale, q, x_out, flag, M, K, ldx, ldo, bit, sigma, qfmt, stream);
+}
+extern "C" int mixq_quant_fused_bf16(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev, uint16_t* x_scale, void* q,
+                                     uint16_t* x_out, int32_t* flag, int M, int K, int ldx, int ldo, int bit, float sigma, int qfmt,
+                                     mixq_stream_t stream)
+{
+    return quant_fused_common<true>(x, ind, n, n_dev, nullptr, x_scale, q, x_out, flag, M, K, ldx, ldo, bit, sigma, qfmt, stream);
 }
 // ... with the caller's kept outlier map of the live `ind` entries (include/mixq_hip.h: bit words, count word, per-column AND-masks): same
 // bytes out from ONE memory round trip - no in-kernel mask build in front of the row maximum, no dependent gather behind the row load
@@ -838,12 +874,21 @@ extern "C" int mixq_quant_fused_masked(uint16_t* x, const int32_t* ind, int n, c
                                        int bit, float sigma, int qfmt, mixq_stream_t stream)
 {
     if (n > 0 && !kept_map_ok(col_mask, map_words, K)) return MIXQ_EINVAL;
-    return quant_fused_common(x, ind, n, n_dev, n > 0 ? col_mask : nullptr, x_scale, q, x_out, flag, M, K, ldx, ldo, bit, sigma, qfmt, stream);
+    return quant_fused_common<false>(x, ind, n, n_dev, n > 0 ? col_mask : nullptr, x_scale, q, x_out, flag, M, K, ldx, ldo, bit, sigma, qfmt, stream);
+}
+extern "C" int mixq_quant_fused_masked_bf16(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev, const uint32_t* col_mask, int map_words,
+                                            uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag, int M, int K, int ldx, int ldo,
+                                            int bit, float sigma, int qfmt, mixq_stream_t stream)
+{
+    if (n > 0 && !kept_map_ok(col_mask, map_words, K)) return MIXQ_EINVAL;
+    return quant_fused_common<true>(x, ind, n, n_dev, n > 0 ? col_mask : nullptr, x_scale, q, x_out, flag, M, K, ldx, ldo, bit, sigma, qfmt, stream);
 }
 
-extern "C" int mixq_quant_known_amax(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev, uint32_t* row_amax,
-                                     const uint32_t* col_mask, int map_words, uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag, int M, int K,
-                                     int ldx, int ldo, int bit, float sigma, int qfmt, mixq_stream_t stream)
+// BF: x, x_out and the row maxima (bit patterns) are bfloat16
+template <bool BF>
+static int quant_known_amax_common(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev, uint32_t* row_amax,
+                                   const uint32_t* col_mask, int map_words, uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag, int M, int K,
+                                   int ldx, int ldo, int bit, float sigma, int qfmt, mixq_stream_t stream)
 {
     if (col_mask && K > 0 && !kept_map_ok(col_mask, map_words, K)) return MIXQ_EINVAL;
     if (qfmt != MIXQ_FMT_PLAIN && qfmt != MIXQ_FMT_P16X64 && qfmt != MIXQ_FMT_F16X64 && !((qfmt == MIXQ_FMT_F6X128 || qfmt == MIXQ_FMT_R6X128) && bit == 4)) return MIXQ_EINVAL;
@@ -859,7 +904,7 @@ extern "C" int mixq_quant_known_amax(uint16_t* x, const int32_t* ind, int n, con
     uint16_t* xo = (n > 0) ? x_out : nullptr;
     const int rows16 = qfmt ? ((M + 15) & ~15) : 0, nchunk = K >> 3;
     hipStream_t st = mixq_stream(stream);
-#define MIXQ_QK(BITv, TPRv, NCHv) hipLaunchKernelGGL((quant_known_kernel<BITv, TPRv, NCHv>), dim3(M), dim3(TPRv), static_cast<size_t>(K <= 30000 ? K : 0) * 2 + 16, st, x, col_mask, row_amax, n_dev, ind, \
+#define MIXQ_QK(BITv, TPRv, NCHv) hipLaunchKernelGGL((quant_known_kernel<BITv, TPRv, NCHv, BF>), dim3(M), dim3(TPRv), static_cast<size_t>(K <= 30000 ? K : 0) * 2 + 16, st, x, col_mask, row_amax, n_dev, ind, \
                                                      ldx, K, n, ldo, x_scale, q, xo, flag, thr, rows16, qfmt)
 #define MIXQ_QK_BY_SIZE(BITv)                                             \
     if      (nchunk <= 256)      MIXQ_QK(BITv, 256, 1);                   \
@@ -874,6 +919,18 @@ extern "C" int mixq_quant_known_amax(uint16_t* x, const int32_t* ind, int n, con
 #undef MIXQ_QK
     return mixq_launch_status();
 }
+extern "C" int mixq_quant_known_amax(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev, uint32_t* row_amax,
+                                     const uint32_t* col_mask, int map_words, uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag, int M, int K,
+                                     int ldx, int ldo, int bit, float sigma, int qfmt, mixq_stream_t stream)
+{
+    return quant_known_amax_common<false>(x, ind, n, n_dev, row_amax, col_mask, map_words, x_scale, q, x_out, flag, M, K, ldx, ldo, bit, sigma, qfmt, stream);
+}
+extern "C" int mixq_quant_known_amax_bf16(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev, uint32_t* row_amax,
+                                          const uint32_t* col_mask, int map_words, uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag, int M, int K,
+                                          int ldx, int ldo, int bit, float sigma, int qfmt, mixq_stream_t stream)
+{
+    return quant_known_amax_common<true>(x, ind, n, n_dev, row_amax, col_mask, map_words, x_scale, q, x_out, flag, M, K, ldx, ldo, bit, sigma, qfmt, stream);
+}
 
 extern "C" int mixq_extract_outliers_zero(uint16_t* x, const int32_t* ind, int n, uint16_t* x_out, int M, int K, int ldx,
                                           int ldo, mixq_stream_t stream)
@@ -884,9 +941,16 @@ extern "C" int mixq_extract_outliers_zero(uint16_t* x, const int32_t* ind, int n
     hipLaunchKernelGGL(extract_kernel, dim3(M), dim3(QT), 0, mixq_stream(stream), x, ldx, ind, n, x_out, ldo);
     return mixq_launch_status();
 }
+// the extraction moves 16-bit patterns and writes zeros (+0 in either container): the fp16 kernel serves bf16 as it is
+extern "C" int mixq_extract_outliers_zero_bf16(uint16_t* x, const int32_t* ind, int n, uint16_t* x_out, int M, int K, int ldx,
+                                               int ldo, mixq_stream_t stream)
+{
+    return mixq_extract_outliers_zero(x, ind, n, x_out, M, K, ldx, ldo, stream);
+}
 
-extern "C" int mixq_detect_outlier_cols(const uint16_t* x, float sigma, uint8_t* colflags, int32_t* ind_out, int32_t* count,
-                                        int M, int K, int ldx, mixq_stream_t stream)
+template <bool BF>
+static int detect_outlier_cols_common(const uint16_t* x, float sigma, uint8_t* colflags, int32_t* ind_out, int32_t* count,
+                                      int M, int K, int ldx, mixq_stream_t stream)
 {
     if (!x || !colflags || !ind_out || !count || M < 0 || K <= 0) return MIXQ_EINVAL;
     if ((K & 7) || (ldx & 7) || ldx < K) return MIXQ_ESHAPE;
@@ -895,12 +959,22 @@ extern "C" int mixq_detect_outlier_cols(const uint16_t* x, float sigma, uint8_t*
     if (e != hipSuccess) return static_cast<int>(e);
     if (M > 0) {
         dim3 g((K / 8 + QT - 1) / QT, (M + DET_ROWS - 1) / DET_ROWS);
-        hipLaunchKernelGGL(detect_cols_kernel, g, dim3(QT), 0, st, x, ldx, M, K, fp16_round(sigma), colflags);
+        hipLaunchKernelGGL(detect_cols_kernel<BF>, g, dim3(QT), 0, st, x, ldx, M, K, fp16_round(sigma), colflags);
         int rc = mixq_launch_status();
         if (rc) return rc;
     }
     hipLaunchKernelGGL(compact_cols_kernel, dim3(1), dim3(CT), 0, st, colflags, K, ind_out, count);
     return mixq_launch_status();
+}
+extern "C" int mixq_detect_outlier_cols(const uint16_t* x, float sigma, uint8_t* colflags, int32_t* ind_out, int32_t* count,
+                                        int M, int K, int ldx, mixq_stream_t stream)
+{
+    return detect_outlier_cols_common<false>(x, sigma, colflags, ind_out, count, M, K, ldx, stream);
+}
+extern "C" int mixq_detect_outlier_cols_bf16(const uint16_t* x, float sigma, uint8_t* colflags, int32_t* ind_out, int32_t* count,
+                                             int M, int K, int ldx, mixq_stream_t stream)
+{
+    return detect_outlier_cols_common<true>(x, sigma, colflags, ind_out, count, M, K, ldx, stream);
 }
 
 extern "C" int mixq_dequant_weight_cols(const void* w, const uint16_t* scale_col, const int32_t* ind, int n, uint16_t* out,

@@ -190,11 +190,23 @@ def _weight_for_gemm(q_w, bit):
     return e[1]
 
 
+def _act_suffix(x, who):
+    """Entry-point suffix of an activation tensor's 16-bit container: "" for float16 (the reference's), "_bf16" for bfloat16 (the
+    `_bf16` twins of include/mixq_hip.h: same arguments, x / x_out read and written as bfloat16, x_scale still fp16)."""
+    if x.dtype == torch.float16:
+        return ""
+    if x.dtype == torch.bfloat16:
+        return "_bf16"
+    raise RuntimeError(f"{who}: x must be float16 or bfloat16, got {x.dtype}")
+
+
 def FindRowScale(x, x_scale, M, K, bit=8):
-    """mixlib.FindRowScale(x, x_scale, M, K, bit) -> q_x  (linear.py:190-193).  Writes x_scale[0:M] in place."""
+    """mixlib.FindRowScale(x, x_scale, M, K, bit) -> q_x  (linear.py:190-193).  Writes x_scale[0:M] in place.  x may be bfloat16
+    (x_scale stays float16)."""
     _dev_check(x, x_scale)
-    if x.dtype != torch.float16 or x_scale.dtype != torch.float16:
-        raise RuntimeError("FindRowScale: x and x_scale must be float16")
+    sfx = _act_suffix(x, "FindRowScale")
+    if x_scale.dtype != torch.float16:
+        raise RuntimeError("FindRowScale: x_scale must be float16")
     x2 = x.reshape(-1, x.shape[-1])
     xp, ldx = _rows(x2, "x")
     if x2.shape[0] < M or x2.shape[1] != K or x_scale.numel() < M:
@@ -220,10 +232,10 @@ def FindRowScale(x, x_scale, M, K, bit=8):
         _flush_pending_extract()
     if _cfg.packed_operands and M > 0 and KB % 64 == 0:
         buf = torch.empty((packed_rows(M), KB), dtype=dt, device=x.device)
-        _capi.call("mixq_find_row_scale", xp, x_scale.data_ptr(), buf.data_ptr(), M, K, ldx, bit, FMT_P16X64, _stream())
+        _capi.call("mixq_find_row_scale" + sfx, xp, x_scale.data_ptr(), buf.data_ptr(), M, K, ldx, bit, FMT_P16X64, _stream())
         return set_fmt(buf[:M], FMT_P16X64)              # same storage, same base pointer: an opaque handle of the reference's shape
     q = torch.empty((M, KB), dtype=dt, device=x.device)
-    _capi.call("mixq_find_row_scale", xp, x_scale.data_ptr(), q.data_ptr(), M, K, ldx, bit, FMT_PLAIN, _stream())
+    _capi.call("mixq_find_row_scale" + sfx, xp, x_scale.data_ptr(), q.data_ptr(), M, K, ldx, bit, FMT_PLAIN, _stream())
     return q
 
 
@@ -371,11 +383,13 @@ class PendingOutlierProduct(torch.Tensor):
 
 
 def ExtractOutliersAndSetToZeros(ind, x):
-    """mixlib.ExtractOutliersAndSetToZeros(ind, x) -> x_out [M,n]; zeroes columns `ind` of x IN PLACE (linear.py:189,205)."""
+    """mixlib.ExtractOutliersAndSetToZeros(ind, x) -> x_out [M,n]; zeroes columns `ind` of x IN PLACE (linear.py:189,205).  A bfloat16 x
+    gives a bfloat16 x_out (the fused_outliers route stays float16)."""
     global _pending_extract
     _dev_check(ind, x)
-    if x.dtype != torch.float16:
-        raise RuntimeError("ExtractOutliersAndSetToZeros: x must be float16")
+    sfx = _act_suffix(x, "ExtractOutliersAndSetToZeros")
+    if sfx and _cfg.fused_outliers:
+        raise RuntimeError("ExtractOutliersAndSetToZeros: configure(fused_outliers=True) takes float16 x only")
     ind = _check_ind(ind, "ExtractOutliersAndSetToZeros")
     xp, ldx = _rows(x, "x")
     M, K = x.shape
@@ -390,9 +404,9 @@ def ExtractOutliersAndSetToZeros(ind, x):
             return out
         _capi.call("mixq_extract_outliers_zero", xp, ind.data_ptr(), n, buf.data_ptr(), M, K, ldx, buf.shape[1], _stream())
         return out
-    out = torch.empty((M, n), dtype=torch.float16, device=x.device)
+    out = torch.empty((M, n), dtype=x.dtype, device=x.device)
     if n:
-        _capi.call("mixq_extract_outliers_zero", xp, ind.data_ptr(), n, out.data_ptr(), M, K, ldx, n, _stream())
+        _capi.call("mixq_extract_outliers_zero" + sfx, xp, ind.data_ptr(), n, out.data_ptr(), M, K, ldx, n, _stream())
     return out
 
 
@@ -667,13 +681,13 @@ def QuantFused(x, ind, x_scale, bit, sigma, x_out=None, flag=None, n_dev=None, p
     FMT_F16X64 (or packed=True: P16x64) q_x is emitted directly in that layout ([roundup(M,16), KB] bytes) and tagged.
     `n_dev` (device int32[1]) overrides the count: `ind` then is a buffer of capacity ind.numel().
     `col_mask`: the caller's kept outlier map of the live `ind` entries (device int32 words - bit words, count word, per-column AND-masks:
-    include/mixq_hip.h, linear.kept_outlier_map) - the pass then needs ONE memory round trip (mixq_quant_fused_masked; same bytes out)."""
+    include/mixq_hip.h, linear.kept_outlier_map) - the pass then needs ONE memory round trip (mixq_quant_fused_masked; same bytes out).
+    A bfloat16 x runs the `_bf16` twins: x_out is then bfloat16, x_scale stays float16."""
     _dev_check(x, x_scale, ind, col_mask)
     fmt = _want_fmt(packed, fmt)
     xp, ldx = _rows(x, "x")
     M, K = x.shape
-    if x.dtype != torch.float16:
-        raise RuntimeError("QuantFused: x must be float16")
+    sfx = _act_suffix(x, "QuantFused")
     if x_scale.numel() < M:
         raise RuntimeError(f"QuantFused: x_scale holds {x_scale.numel()} rows, the batch has {M} (MixLibCache.inputdim too small)")
     n = 0 if ind is None else ind.numel()
@@ -683,36 +697,40 @@ def QuantFused(x, ind, x_scale, bit, sigma, x_out=None, flag=None, n_dev=None, p
         ind = _check_ind(ind, "QuantFused")
         if x_out is None:
             ldo = (n + 15) // 16 * 16
-            x_out = torch.empty((M, ldo), dtype=torch.float16, device=x.device)
+            x_out = torch.empty((M, ldo), dtype=x.dtype, device=x.device)
+        elif x_out.dtype != x.dtype:
+            raise RuntimeError(f"QuantFused: x_out must be {x.dtype} like x, got {x_out.dtype}")
         op, ldo = _rows(x_out, "x_out")
         ip = ind.data_ptr()
     else:
         op, ldo, ip = None, 0, None
     if col_mask is not None and n:
         _check_kept_map(col_mask, K, "QuantFused")
-        _capi.call("mixq_quant_fused_masked", xp, ip, n, _ptr(n_dev), col_mask.data_ptr(), col_mask.numel(), x_scale.data_ptr(), q.data_ptr(), op, _ptr(flag), M, K,
+        _capi.call("mixq_quant_fused_masked" + sfx, xp, ip, n, _ptr(n_dev), col_mask.data_ptr(), col_mask.numel(), x_scale.data_ptr(), q.data_ptr(), op, _ptr(flag), M, K,
                    ldx, ldo, bit, float(sigma), fmt, _stream())
     else:
-        _capi.call("mixq_quant_fused", xp, ip, n, _ptr(n_dev), x_scale.data_ptr(), q.data_ptr(), op, _ptr(flag), M, K, ldx,
+        _capi.call("mixq_quant_fused" + sfx, xp, ip, n, _ptr(n_dev), x_scale.data_ptr(), q.data_ptr(), op, _ptr(flag), M, K, ldx,
                    ldo, bit, float(sigma), fmt, _stream())
     return set_fmt(q, fmt), (x_out[:, :n] if n else None)
 
 
 def FindRowScalePacked(x, x_scale, M, K, bit=8, fmt=FMT_P16X64):
-    """FindRowScale emitting a packed layout."""
+    """FindRowScale emitting a packed layout (x float16 or bfloat16)."""
     _dev_check(x, x_scale)
+    sfx = _act_suffix(x, "FindRowScalePacked")
     xp, ldx = _rows(x, "x")
     if x_scale.numel() < M:
         raise RuntimeError(f"FindRowScalePacked: x_scale holds {x_scale.numel()} rows, the batch has {M}")
     q = torch.empty((packed_rows(M), _q_row_bytes(K, bit, fmt)), dtype=torch.int8 if bit == 8 else torch.uint8, device=x.device)
-    _capi.call("mixq_find_row_scale", xp, x_scale.data_ptr(), q.data_ptr(), M, K, ldx, bit, fmt, _stream())
+    _capi.call("mixq_find_row_scale" + sfx, xp, x_scale.data_ptr(), q.data_ptr(), M, K, ldx, bit, fmt, _stream())
     return set_fmt(q, fmt)
 
 
 def DetectOutlierCols(x, sigma, scratch=None):
     """Device-side FindOutliers (linear.py:157-161): returns (ind_buf int32 [K], count int32 [1]) on device; the
-    caller reads `count` (a host sync, warm-up only) and slices."""
+    caller reads `count` (a host sync, warm-up only) and slices.  x float16 or bfloat16 (|x| > fp16(sigma) in either)."""
     _dev_check(x)
+    sfx = _act_suffix(x, "DetectOutlierCols")
     xp, ldx = _rows(x, "x")
     M, K = x.shape
     if scratch is None:
@@ -720,7 +738,7 @@ def DetectOutlierCols(x, sigma, scratch=None):
                    torch.empty(K, dtype=torch.int32, device=x.device),
                    torch.zeros(1, dtype=torch.int32, device=x.device))
     flags, ind_buf, count = scratch
-    _capi.call("mixq_detect_outlier_cols", xp, float(sigma), flags.data_ptr(), ind_buf.data_ptr(), count.data_ptr(), M, K,
+    _capi.call("mixq_detect_outlier_cols" + sfx, xp, float(sigma), flags.data_ptr(), ind_buf.data_ptr(), count.data_ptr(), M, K,
                ldx, _stream())
     return ind_buf, count
 
