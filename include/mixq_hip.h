@@ -112,7 +112,24 @@ int mixq_device_info(char* buf_host, int cap);
  * mixq_selftest_quant_exact_bf16).  A row whose inlier maximum exceeds 65504 * qmax has no finite fp16 scale: outside the supported
  * range.  The outlier columns (x_out) carry the bf16 values unchanged, whatever their magnitude.  Outlier detection flags
  * |x| > fp16(sigma) as for fp16.  Defined for: mixq_find_row_scale, mixq_extract_outliers_zero, mixq_quant_fused(_masked),
- * mixq_quant_known_amax (row_amax then holds maxima of bf16 bit patterns), mixq_detect_outlier_cols, mixq_selftest_quant_exact. */
+ * mixq_quant_known_amax (row_amax then holds maxima of bf16 bit patterns), mixq_detect_outlier_cols, mixq_selftest_quant_exact.
+ *
+ * ---- bf16 layers (ABI 1.2): the GEMM side ----
+ * mixq_gemm_i8_fused_bf16, mixq_gemm_i4_fused_bf16, mixq_gemm_i8_fused_amax_bf16, mixq_gemm_amax_supported_bf16, mixq_linear_forward_bf16.
+ * One dtype per model: a bf16 layer takes bf16 x and writes bf16 y.
+ *   bfloat16: x, x_out, w_out, addend (the multiplier of MIXQ_ACT_SILU_MUL included), y
+ *   fp16 as ever: x_scale, scale_col, bias (and sigma's rounding)
+ * w_out is the caller's bf16 IMAGE of the layer's fp16 outlier-column weights, RNE_bf16(weight_cache): one rounding that drops three
+ * significand bits of each outlier-column weight (the tail runs on v_mfma_f32_16x16x32_bf16, whose operands are both bf16).
+ * The epilogue is the fp16 one with the container swapped, fp32 throughout and ONE rounding (v_cvt_pk_bf16_f32, RNE):
+ *   z = acc * float(sx[m]) * float(sw[n]) + sum_j float(xo[m,j]) * float(wo[n,j]) + float(addend[m,n])
+ *   y = bf16( act(z) + float(bias[n]) );   MIXQ_ACT_SILU_MUL: y = bf16( (silu(z') + bias) * float(addend) ), z' without the addend
+ * The row-maximum side output maximises the bf16 bit patterns |y| & 0x7fff (order-preserving for bf16 as for fp16); it feeds
+ * mixq_quant_known_amax_bf16.  Pad columns of x_out / w_out (>= n_out) may hold anything, NaN patterns included: they are masked.
+ * Served layouts: MIXQ_X_PACKED | MIXQ_W_F16X64 (int8) and MIXQ_XW_F6X128 (4-bit), at every batch size, by the weights-in-registers
+ * kernels; plain / P16X64 layouts, nibble-packed int4 and MIXQ_ACT_SILU_PAIR answer MIXQ_ESHAPE.  A configuration forced with
+ * mixq_gemm_set_config that has no bf16 form answers MIXQ_EINVAL before any launch.  Not (yet) in bf16: mixq_rmsnorm*,
+ * mixq_gemm_w8a16, mixq_gemm_i8 / mixq_dequant. */
 
 /* ---- (i) per-token absmax + quantise ------------------------------------------------------------------
  * Replaces mixlib.FindRowScale(x, x_scale, M, K, bit) -> q_x   (linear.py:190-193, :221).
@@ -217,6 +234,12 @@ int mixq_gemm_i8_fused(const int8_t* q_x, const int8_t* q_w, const uint16_t* x_s
                        const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
                        const uint16_t* addend, int lda, const uint16_t* bias,
                        uint16_t* y, int ldy, int M, int N, int K, int act, int layout, mixq_stream_t stream);
+/* x_out, w_out, addend, y: bfloat16; x_scale, scale_col, bias: fp16.  layout: MIXQ_X_PACKED | MIXQ_W_F16X64 only ("bf16 layers" above) */
+int mixq_gemm_i8_fused_bf16(const int8_t* q_x, const int8_t* q_w, const uint16_t* x_scale,
+                            const uint16_t* scale_col, const uint16_t* x_out, int ldxo,
+                            const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
+                            const uint16_t* addend, int lda, const uint16_t* bias,
+                            uint16_t* y, int ldy, int M, int N, int K, int act, int layout, mixq_stream_t stream);
 
 /* Same for nibble-packed operands: replaces mixlib.int4FusedDequantize[Silu](..., M, N, K/2)
  * (linear.py:259-265, 278-283, 360-366).  q_x uint8 [M,K/2], q_w uint8 [N,K/2]; K is the LOGICAL depth
@@ -226,6 +249,12 @@ int mixq_gemm_i4_fused(const uint8_t* q_x, const uint8_t* q_w, const uint16_t* x
                        const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
                        const uint16_t* addend, int lda, const uint16_t* bias,
                        uint16_t* y, int ldy, int M, int N, int K, int act, int layout, mixq_stream_t stream);
+/* x_out, w_out, addend, y: bfloat16; x_scale, scale_col, bias: fp16.  layout: MIXQ_XW_F6X128 only ("bf16 layers" above) */
+int mixq_gemm_i4_fused_bf16(const uint8_t* q_x, const uint8_t* q_w, const uint16_t* x_scale,
+                            const uint16_t* scale_col, const uint16_t* x_out, int ldxo,
+                            const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
+                            const uint16_t* addend, int lda, const uint16_t* bias,
+                            uint16_t* y, int ldy, int M, int N, int K, int act, int layout, mixq_stream_t stream);
 
 /* ---- the next layer's row maximum as a side output of the producing GEMM ------------------------------------------------
  * down_proj's pre-pass (linear.py:187-193) needs max_k |x[m,k]| over the columns it does not extract - a full pass over the
@@ -246,6 +275,14 @@ int mixq_gemm_i8_fused_amax(const int8_t* q_x, const int8_t* q_w, const uint16_t
                             uint16_t* y, int ldy, int M, int N, int K, int act, int layout,
                             uint32_t* row_amax, const uint32_t* col_mask, mixq_stream_t stream);
 int mixq_gemm_amax_supported(int M, int N, int K, int layout);
+/* x_out, w_out, addend, y: bfloat16; row_amax: maxima of the bf16 bit patterns |y| & 0x7fff (for mixq_quant_known_amax_bf16) */
+int mixq_gemm_i8_fused_amax_bf16(const int8_t* q_x, const int8_t* q_w, const uint16_t* x_scale,
+                                 const uint16_t* scale_col, const uint16_t* x_out, int ldxo,
+                                 const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
+                                 const uint16_t* addend, int lda, const uint16_t* bias,
+                                 uint16_t* y, int ldy, int M, int N, int K, int act, int layout,
+                                 uint32_t* row_amax, const uint32_t* col_mask, mixq_stream_t stream);
+int mixq_gemm_amax_supported_bf16(int M, int N, int K, int layout);   /* every batch size: the bf16 forms have no small-batch exception */
 int mixq_quant_known_amax(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev, uint32_t* row_amax,
                           const uint32_t* col_mask, int map_words, uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag,
                           int M, int K, int ldx, int ldo, int bit, float sigma, int qfmt, mixq_stream_t stream);
@@ -279,6 +316,9 @@ typedef struct mixq_linear_args {
     int col_mask_words;                             /* int32 words behind col_mask: >= mixq_kept_map_words(K) (checked whenever col_mask is used) */
 } mixq_linear_args;
 int mixq_linear_forward(const mixq_linear_args* args, mixq_stream_t stream);
+/* The same block with x, x_out, w_out, addend and y holding bfloat16 (x_scale, scale_col, bias fp16): the _bf16 quantise pass, then the
+ * _bf16 GEMM; bit-identical to those two calls.  wfmt must be MIXQ_FMT_F16X64 or MIXQ_FMT_F6X128 (else MIXQ_ESHAPE, before anything runs). */
+int mixq_linear_forward_bf16(const mixq_linear_args* args, mixq_stream_t stream);
 
 /* ---- operand re-tiling ------------------------------------------------------------------------------------
  * Copy a plain [R,KB] byte matrix (int8 weights, or nibble-packed int4) into MIXQ_FMT_P16X64.

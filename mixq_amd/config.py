@@ -9,6 +9,8 @@ from __future__ import annotations
 
 from dataclasses import dataclass, replace
 
+import torch
+
 from ._capi import FMT_F16X64, FMT_F6X128
 
 
@@ -38,10 +40,19 @@ class MixqConfig:
     # the fused norm hands the next (frozen) layer's kept outlier map to its quantise step (mixq_rmsnorm_quant_fused_masked); False = the
     # column mask is built inside the kernel on every launch
     norm_kept_map: bool = True
+    # The model's activation dtype: ONE per model.  A layer takes x of exactly this dtype and returns y in it (torch.float16, the
+    # reference's, or torch.bfloat16: DESIGN.md section 2).  x_scale, scale_col, bias, sigma and the weight_cache buffer are float16 in
+    # either case; y, x_out / activation_outliers and an addend / multiplier follow this switch.  Served in bfloat16: MixLinear_GEMM
+    # (W8A8 and W4A4); not (yet): weight_only layers, MixLlamaMLP's fused routes, the fused RMSNorm.
+    act_dtype: torch.dtype = torch.float16
+
+    def __post_init__(self):
+        if self.act_dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"MixqConfig: act_dtype must be torch.float16 or torch.bfloat16, got {self.act_dtype}")
 
     def copy(self, **changes) -> "MixqConfig":
         return replace(self, **changes)
 
     def key(self):
         """What of the configuration is part of a kept plan's / joint image's identity."""
-        return (self.pack_fmt, self.pack_fmt4, self.small_batch_m4)
+        return (self.pack_fmt, self.pack_fmt4, self.small_batch_m4, self.act_dtype)

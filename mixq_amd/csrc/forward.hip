@@ -5,7 +5,8 @@
 // is what an eager decoder loop pays per layer.  Replaces the steady state of /root/reference/mixquant/modules/linear.py:187-193 + :244-285.
 #include "common.h"
 
-extern "C" int mixq_linear_forward(const mixq_linear_args* a, mixq_stream_t stream)
+template <bool BF>
+static int linear_forward(const mixq_linear_args* a, mixq_stream_t stream)
 {
     if (!a) return MIXQ_EINVAL;
     if (a->bit != 8 && a->bit != 4) return MIXQ_EINVAL;
@@ -17,6 +18,7 @@ extern "C" int mixq_linear_forward(const mixq_linear_args* a, mixq_stream_t stre
         case MIXQ_FMT_F6X128: layout = MIXQ_XW_F6X128; break;       // W4A4 on the FP6 matrix pipe: both operands as FP6 codes (activations: R6X128)
         default: return MIXQ_EINVAL;
     }
+    if (BF && a->wfmt != MIXQ_FMT_F16X64 && a->wfmt != MIXQ_FMT_F6X128) return MIXQ_ESHAPE;   // (the bf16 GEMMs: weights-in-registers layouts only; said before the quantise pass runs)
     if ((a->wfmt == MIXQ_FMT_F6X128) != (a->qfmt == MIXQ_FMT_R6X128)) return MIXQ_EINVAL;    // FP6 weights go with row-contiguous FP6 activations
     if (a->wfmt == MIXQ_FMT_F6X128) { if (a->bit != 4) return MIXQ_EINVAL; }
     else if (a->qfmt == MIXQ_FMT_P16X64) layout |= MIXQ_X_PACKED;
@@ -25,19 +27,23 @@ extern "C" int mixq_linear_forward(const mixq_linear_args* a, mixq_stream_t stre
     const bool outl = a->n_cap > 0 && a->x_out && a->w_out;
     if (a->n_cap > 0 && !outl) return MIXQ_EINVAL;                  // known outlier columns need both operands of the tail
     int rc = a->row_amax
-        ? mixq_quant_known_amax(a->x, a->ind, a->n_cap, a->n_dev, a->row_amax, a->col_mask, a->col_mask_words, a->x_scale, a->q_x, a->x_out, a->flag, a->M,
+        ? (BF ? mixq_quant_known_amax_bf16 : mixq_quant_known_amax)(a->x, a->ind, a->n_cap, a->n_dev, a->row_amax, a->col_mask, a->col_mask_words, a->x_scale, a->q_x, a->x_out, a->flag, a->M,
                                 a->K, a->ldx, a->ldxo, a->bit, a->sigma, a->qfmt, stream)
         : (a->col_mask && a->n_cap > 0         // a frozen layer keeps the mask of its outlier columns: no mask build in front of the row maximum
-           ? mixq_quant_fused_masked(a->x, a->ind, a->n_cap, a->n_dev, a->col_mask, a->col_mask_words, a->x_scale, a->q_x, a->x_out, a->flag, a->M, a->K, a->ldx,
+           ? (BF ? mixq_quant_fused_masked_bf16 : mixq_quant_fused_masked)(a->x, a->ind, a->n_cap, a->n_dev, a->col_mask, a->col_mask_words, a->x_scale, a->q_x, a->x_out, a->flag, a->M, a->K, a->ldx,
                                      a->ldxo, a->bit, a->sigma, a->qfmt, stream)
-           : mixq_quant_fused(a->x, a->ind, a->n_cap, a->n_dev, a->x_scale, a->q_x, a->x_out, a->flag, a->M, a->K, a->ldx, a->ldxo,
+           : (BF ? mixq_quant_fused_bf16 : mixq_quant_fused)(a->x, a->ind, a->n_cap, a->n_dev, a->x_scale, a->q_x, a->x_out, a->flag, a->M, a->K, a->ldx, a->ldxo,
                               a->bit, a->sigma, a->qfmt, stream));
     if (rc) return rc;
     if (a->bit == 8)
-        return mixq_gemm_i8_fused(static_cast<const int8_t*>(a->q_x), static_cast<const int8_t*>(a->q_w), a->x_scale, a->scale_col,
+        return (BF ? mixq_gemm_i8_fused_bf16 : mixq_gemm_i8_fused)(static_cast<const int8_t*>(a->q_x), static_cast<const int8_t*>(a->q_w), a->x_scale, a->scale_col,
                                   a->x_out, a->ldxo, a->w_out, a->ldwo, a->n_cap, a->n_dev, a->addend, a->lda, a->bias, a->y, a->ldy,
                                   a->M, a->N, a->K, a->act, layout, stream);
-    return mixq_gemm_i4_fused(static_cast<const uint8_t*>(a->q_x), static_cast<const uint8_t*>(a->q_w), a->x_scale, a->scale_col,
+    return (BF ? mixq_gemm_i4_fused_bf16 : mixq_gemm_i4_fused)(static_cast<const uint8_t*>(a->q_x), static_cast<const uint8_t*>(a->q_w), a->x_scale, a->scale_col,
                               a->x_out, a->ldxo, a->w_out, a->ldwo, a->n_cap, a->n_dev, a->addend, a->lda, a->bias, a->y, a->ldy,
                               a->M, a->N, a->K, a->act, layout, stream);
 }
+
+extern "C" int mixq_linear_forward(const mixq_linear_args* a, mixq_stream_t stream) { return linear_forward<false>(a, stream); }
+// ... with bf16 x, x_out, w_out, addend and y: the _bf16 quantise pass, then the _bf16 GEMM (layouts F16X64 / F6X128 weights; others: MIXQ_ESHAPE)
+extern "C" int mixq_linear_forward_bf16(const mixq_linear_args* a, mixq_stream_t stream) { return linear_forward<true>(a, stream); }

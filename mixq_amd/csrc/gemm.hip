@@ -982,7 +982,85 @@ int gemm_fused_common(const void* q_x, const void* q_w, const uint16_t* x_scale,
     return launch_gemm(a, bit == 8 ? 0 : 1, mixq_stream(stream));
 }
 
+// The bf16 forms (include/mixq_hip.h, "bf16 layers"): x_out, w_out, addend and y are bfloat16; scales and bias stay fp16.  Served by the
+// weights-in-registers kernels only - int8 as MIXQ_X_PACKED | MIXQ_W_F16X64, 4-bit as MIXQ_XW_F6X128 - at every batch size (no bf16 form of
+// this file's LDS-staged kernel or of gemm_skinny.hip): other layouts answer MIXQ_ESHAPE, a forced configuration without a bf16 form
+// MIXQ_EINVAL, both before any launch.
+int gemm_fused_bf16(const void* q_x, const void* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
+                    const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
+                    const uint16_t* addend, int lda, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int K,
+                    int act, int layout, int bit, mixq_stream_t stream, uint32_t* row_amax = nullptr, const uint32_t* amax_mask = nullptr)
+{
+    const bool f6 = layout == MIXQ_XW_F6X128;
+    if (f6 && bit != 4) return MIXQ_EINVAL;
+    if (!f6 && (layout & ~(MIXQ_X_PACKED | MIXQ_W_PACKED | MIXQ_W_F16X64))) return MIXQ_EINVAL;
+    if (M < 0 || N < 0 || K <= 0 || n_out < 0) return MIXQ_EINVAL;
+    if (M > 0 && N > 0 && (!q_x || !q_w || !x_scale || !scale_col || !y)) return MIXQ_EINVAL;
+    if (act != MIXQ_ACT_NONE && act != MIXQ_ACT_SILU && act != MIXQ_ACT_SILU_MUL && act != MIXQ_ACT_SILU_PAIR) return MIXQ_EINVAL;
+    if (act == MIXQ_ACT_SILU_MUL && !addend) return MIXQ_EINVAL;            // the multiplier is mandatory
+    if (act == MIXQ_ACT_SILU_PAIR) return MIXQ_ESHAPE;                      // (the joint gate / up form is fp16 only)
+    if (!(f6 || (bit == 8 && layout == (MIXQ_X_PACKED | MIXQ_W_F16X64)))) return MIXQ_ESHAPE;
+    if (f6 && row_amax) return MIXQ_ESHAPE;
+    const int KB = bit == 8 ? K : K / 2;
+    if ((KB % 64) || (bit == 4 && (K & 1)) || (N & 3) || (ldy & 3) || ldy < N) return MIXQ_ESHAPE;
+    if (addend && lda != 0 && lda < N) return MIXQ_EINVAL;
+    if (n_out > 0 && x_out && w_out) {
+        const int need = (n_out + 15) & ~15;
+        if (ldxo < need || ldwo < need || (ldxo & 7) || (ldwo & 7)) return MIXQ_ESHAPE;
+    }
+    const int wbit = f6 ? 6 : 8;
+    const int wr0 = NUM_CFGS + mixq_sk_num_configs() + 1;
+    const int g_forced = g_forced_cfg.get();                     // this device's forced configuration (-1: automatic)
+    if (g_forced >= 0 && (g_forced < wr0 || !mixq_wr_has_bf16(wbit, g_forced - wr0))) return MIXQ_EINVAL;
+    if (M == 0 || N == 0) return MIXQ_OK;
+    const int c = g_forced >= 0 ? g_forced - wr0 : mixq_wr_pick_bf16(wbit, M, N, KB);
+    if (c < 0) return MIXQ_ESHAPE;                               // (no tiling with a bf16 form serves the problem)
+    int n1 = 0, c2 = -1;
+    // a partial last round of tiles: two launches as for fp16, when both tilings have bf16 forms
+    if (g_forced == -1 && mixq_wr_split(wbit, M, N, KB, c, &n1, &c2) && mixq_wr_has_bf16(wbit, c2)) {
+        if (int rc = mixq_wr_launch(c, wbit, q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
+                                    ldy, M, N, KB, act, nullptr, mixq_stream(stream), row_amax, amax_mask, 0, n1, true)) return rc;
+        return mixq_wr_launch(c2, wbit, q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
+                              ldy, M, N, KB, act, nullptr, mixq_stream(stream), row_amax, amax_mask, n1, N - n1, true);
+    }
+    return mixq_wr_launch(c, wbit, q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
+                          ldy, M, N, KB, act, nullptr, mixq_stream(stream), row_amax, amax_mask, 0, -1, true);
+}
+
 }  // namespace
+
+extern "C" int mixq_gemm_i8_fused_bf16(const int8_t* q_x, const int8_t* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
+                                       const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out,
+                                       const int32_t* n_out_dev, const uint16_t* addend, int lda, const uint16_t* bias,
+                                       uint16_t* y, int ldy, int M, int N, int K, int act, int layout, mixq_stream_t stream)
+{
+    return gemm_fused_bf16(q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
+                           ldy, M, N, K, act, layout, 8, stream);
+}
+extern "C" int mixq_gemm_i4_fused_bf16(const uint8_t* q_x, const uint8_t* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
+                                       const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out,
+                                       const int32_t* n_out_dev, const uint16_t* addend, int lda, const uint16_t* bias,
+                                       uint16_t* y, int ldy, int M, int N, int K, int act, int layout, mixq_stream_t stream)
+{
+    return gemm_fused_bf16(q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
+                           ldy, M, N, K, act, layout, 4, stream);
+}
+// (row_amax then holds maxima of bf16 bit patterns: what mixq_quant_known_amax_bf16 reads)
+extern "C" int mixq_gemm_i8_fused_amax_bf16(const int8_t* q_x, const int8_t* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
+                                            const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out,
+                                            const int32_t* n_out_dev, const uint16_t* addend, int lda, const uint16_t* bias,
+                                            uint16_t* y, int ldy, int M, int N, int K, int act, int layout, uint32_t* row_amax,
+                                            const uint32_t* col_mask, mixq_stream_t stream)
+{
+    if (!row_amax) return MIXQ_EINVAL;
+    return gemm_fused_bf16(q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
+                           ldy, M, N, K, act, layout, 8, stream, row_amax, col_mask);
+}
+// (every batch size runs a weights-in-registers tiling in bf16: no small-batch exception)
+extern "C" int mixq_gemm_amax_supported_bf16(int M, int N, int K, int layout)
+{
+    return (M > 0 && N > 0 && K > 0 && (K % 64) == 0 && (N & 3) == 0 && layout == (MIXQ_X_PACKED | MIXQ_W_F16X64)) ? 1 : 0;
+}
 
 extern "C" int mixq_gemm_i8_fused(const int8_t* q_x, const int8_t* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
                                   const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out,
@@ -1160,7 +1238,7 @@ extern "C" int mixq_gemm_pick_config_fmt(int M, int N, int K, int bit, int fmt) 
     return mixq_gemm_pick_config(M, N, K, bit);
 }
 
-extern "C" int mixq_version(void) { return 1001; }   // 1.1: the _bf16 entry points
+extern "C" int mixq_version(void) { return 1002; }   // 1.1: the _bf16 quantise entry points; 1.2: the _bf16 GEMMs and mixq_linear_forward_bf16
 
 extern "C" int mixq_device_info(char* buf, int cap) {
     if (!buf || cap <= 0) return MIXQ_EINVAL;

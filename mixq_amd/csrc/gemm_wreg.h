@@ -12,7 +12,12 @@ int mixq_wr_launch(int c, int bit, const void* q_x, const void* q_w, const uint1
                    const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
                    const uint16_t* addend, int lda, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int KB, int act,
                    unsigned long long* trace, hipStream_t st, uint32_t* row_amax = nullptr, const uint32_t* amax_mask = nullptr,
-                   int n_begin = 0, int n_cols = -1);     // the launch covers the weight rows [n_begin, n_begin + n_cols) (default: all from n_begin)
+                   int n_begin = 0, int n_cols = -1,      // the launch covers the weight rows [n_begin, n_begin + n_cols) (default: all from n_begin)
+                   bool bf16 = false);                    // x_out, w_out, addend and y are bfloat16 (bit 8 or 6; a tiling without a bf16 form: MIXQ_EINVAL)
+// the bf16 forms: the tiling for a problem (-1: none), and whether a (forced) configuration has one
+int mixq_wr_pick_bf16(int bit, int M, int N, int KB);   // bit: 8, or 6 (int4 as FP6 codes)
+bool mixq_wr_has_bf16(int bit, int c);
+const void* mixq_wr_bf16_kernel(int bit, int c);        // gemm_wreg_bf16.hip: the launch handle of tiling c's bf16 form, or nullptr
 #ifdef MIXQ_TUNING
 // (experiment) the weight image of the launch after the next one: the next launch's loader waves touch it (one launch, this host thread)
 void mixq_wr_hint_next(const void* w, long long bytes);

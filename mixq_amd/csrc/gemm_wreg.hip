@@ -84,6 +84,22 @@ __device__ __forceinline__ void wr_glds16(const uint8_t* gsrc, uint8_t* lds_wave
 }
 __device__ __forceinline__ float wr_silu(float v) { return mixq_silu(v); }   // (common.h: never contracted with the bias addition)
 
+// The 16-bit container of the ACTIVATION-side tensors of an instantiation (x_out / w_out of the outlier tail, addend, y): BF = false is
+// fp16, BF = true bfloat16 (include/mixq_hip.h, "bf16 layers").  These three are everything that differs between the two forms: the tail's
+// MFMA, the widening of the addend, the one rounding of y.  Scales and bias are fp16 in both (h2f).
+typedef __bf16 wr_bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 wr_bf16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 wr_f16x2 __attribute__((ext_vector_type(2)));
+typedef float wr_f32x2 __attribute__((ext_vector_type(2)));
+template <bool BF> __device__ __forceinline__ f32x4 wr_tail_mfma(u32x4 w, u32x4 x, f32x4 c) {
+    if constexpr (BF) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(wr_bf16x8, w), __builtin_bit_cast(wr_bf16x8, x), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
+}
+template <bool BF> __device__ __forceinline__ uint32_t wr_cvt_pk(float lo, float hi) {   // round-to-nearest-even: v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32
+    if constexpr (BF) return __builtin_bit_cast(uint32_t, __builtin_convertvector(wr_f32x2{lo, hi}, wr_bf16x2));
+    else return __builtin_bit_cast(uint32_t, __builtin_convertvector(wr_f32x2{lo, hi}, wr_f16x2));
+}
+
 // compile-time loop: f(std::integral_constant<int, I>{}) for I in [I0, N) (ring slots are compile-time registers)
 template <int I, int N, class F> __device__ __forceinline__ void wr_static_for(F&& f) {
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); wr_static_for<I + 1, N>(f); }
@@ -100,9 +116,22 @@ constexpr int MIXQ_Y_WT_MB = 4;             // tiles of at most this many 16-row
                                             // tiles, and lines written through during the epilogue are not left for the kernel's closing release to write back: -0.1 ... -0.25 us per launch at
                                             // N = 4096 / small batches, nothing at the metric tile, +0.6 % at 2048 tokens if the big tiles did it too (NOTEBOOK.md round 5)
 constexpr int MIXQ_PAIR_ST = 2;             // cache policy of the joint gate / up form's stores of Y: 2 = nt (streaming), 0 = ordinary
-template <int MB, int WNB, int NSTAGE, int D, int Q, int LOADERS, int ABL>
+// BF (the 16-bit container, see wr_tail_mfma above) is a trailing template parameter where this file is compiled as gemm_wreg_bf16.hip - the bf16
+// forms, a translation unit and hence a GPU code object of their own - and the constant `false` in this file's own object, whose kernels keep
+// the seven-argument names they had: the fp16 code object stays BYTE-IDENTICAL to the one before the bf16 forms existed.  That is not
+// tidiness: with both forms in one object the larger symbol tables moved .text - identical instructions - by 13.25 KiB, and the metric
+// shape's forward lost 2.2 % (1596-1614 against 1633-1654 TFLOPS, alternating runs on one box: NOTEBOOK.md, "bf16 layers").
+#ifdef MIXQ_WR_BF16_TU
+#define MIXQ_WR_BF_TPARAM , bool BF
+#else
+#define MIXQ_WR_BF_TPARAM
+#endif
+template <int MB, int WNB, int NSTAGE, int D, int Q, int LOADERS, int ABL MIXQ_WR_BF_TPARAM>
 __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const WrArgs a)
 {
+#ifndef MIXQ_WR_BF16_TU
+    constexpr bool BF = false;
+#endif
     // ABL = 90 is not an ablation but a kernel FORM - the paired gate / up epilogue (PAIR below) on the shipped loop: everywhere else in this
     // body the loop variant is ABLK, which reads 0 for it
     // (ABL 16 / 17 / 18: the feed ablations 3 / 2 / 1 with PSEUDO-RANDOM bytes in the operands that are never loaded - the MFMA's power, hence the clock of a
@@ -197,6 +226,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
     static_assert(!SELF || (LOOK == D + 1 && !I4 && ABLK == 0 && (D - 1) * (WNB + LOADS) < 64), "self-loading form: X stage kt+1 and the weights of k-step kt are requested in the same k-step");
     static_assert(!EPI2 || SC_END <= 160 * 1024, "X ring + tail blocks + panel flags + scales must fit the 160 KiB of LDS");
     static_assert(!PAIR || (EPI2 && (Q == 0 || Q == 3)), "the paired gate / up epilogue exists in the panel form of the int8 and the FP6 tuple-ring kernels");
+    static_assert(!BF || (!PAIR && ABL == 0 && (Q == 0 || Q == 3)), "bf16 forms: the shipped int8 and FP6 tuple-ring loops, no paired epilogue");
 
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     if constexpr (ABLK == 9) { if (a.act != 12345) return; }                      // launch floor of this grid / LDS footprint
@@ -1548,6 +1578,10 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             o[0] = h2f(static_cast<uint16_t>(v.x & 0xffffu)); o[1] = h2f(static_cast<uint16_t>(v.x >> 16));
             o[2] = h2f(static_cast<uint16_t>(v.y & 0xffffu)); o[3] = h2f(static_cast<uint16_t>(v.y >> 16));
         };
+        auto unpack4a = [](u32x2 v, float* o) MIXQ_INL {                        // the addend: in the activation container
+            o[0] = a2f<BF>(static_cast<uint16_t>(v.x & 0xffffu)); o[1] = a2f<BF>(static_cast<uint16_t>(v.x >> 16));
+            o[2] = a2f<BF>(static_cast<uint16_t>(v.y & 0xffffu)); o[3] = a2f<BF>(static_cast<uint16_t>(v.y >> 16));
+        };
 
         if constexpr (EPI2) {
             // ---- EPI2: row panels, software-pipelined, copied out by the loader waves (see the note at its declaration) ----------------
@@ -1660,7 +1694,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                     f32x4 f = fa[j][i];
                     float av[4];
                     if (OPT && has_add) {
-                        unpack4(*reinterpret_cast<const u32x2_u*>(a.addend + static_cast<size_t>(m < a.M ? m : a.M - 1) * a.lda + nc), av);
+                        unpack4a(*reinterpret_cast<const u32x2_u*>(a.addend + static_cast<size_t>(m < a.M ? m : a.M - 1) * a.lda + nc), av);
                         if (!mul_add) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r) f[r] += av[r];
@@ -1678,9 +1712,9 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
 #pragma unroll
                         for (int r = 0; r < 4; ++r) f[r] *= av[r];
                     }
-                    u32x2 o;                                           // round-to-nearest-even, two values per v_cvt_pk_f16_f32
-                    o.x = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{f[0], f[1]}, f16x2));
-                    o.y = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{f[2], f[3]}, f16x2));
+                    u32x2 o;                                           // round-to-nearest-even, two values per v_cvt_pk_f16_f32 (bf16 form: v_cvt_pk_bf16_f32)
+                    o.x = wr_cvt_pk<BF>(f[0], f[1]);
+                    o.y = wr_cvt_pk<BF>(f[2], f[3]);
                     if (OPT && has_amax) {
                         typedef unsigned short us2 __attribute__((ext_vector_type(2)));
                         const us2 mx = __builtin_elementwise_max(__builtin_bit_cast(us2, o.x & keep_lo), __builtin_bit_cast(us2, o.y & keep_hi));
@@ -1744,7 +1778,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             };
             auto tail_mma = [&](int j, int i, u32x4 w, u32x4 x) MIXQ_INL {
                 if constexpr (ABLK == 64) return;                                 // probe: the epilogue without its tail MFMAs (results are garbage)
-                fa[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), fa[j][i], 0, 0, 0);
+                fa[j][i] = wr_tail_mfma<BF>(w, x, fa[j][i]);
             };
             // more than 32 TQ outlier columns (rare: the search stops adding beyond 128, linear.py:224): the remaining k-steps with both
             // operands from global memory, one exposed round trip each
@@ -1919,8 +1953,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             }
         };
         auto tail_mfma1 = [&](int P, int j, int i) MIXQ_INL {
-            fa[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, woq[P][i]), __builtin_bit_cast(f16x8, xoq[P][j]),
-                                                              fa[j][i], 0, 0, 0);
+            fa[j][i] = wr_tail_mfma<BF>(woq[P][i], xoq[P][j], fa[j][i]);
         };
         // PANELS: the fat prefill tile (SELF) holds 256 accumulator registers per lane; dequantised all at once they would need a
         // second 256 - in VGPRs, since the VALU cannot write AGPRs - next to the tail operands (165 spilled registers, and wrong
@@ -1979,7 +2012,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                     f32x4 f = fa[j][i];
                     float av[4];
                     if (OPT && has_add) {
-                        unpack4(*reinterpret_cast<const u32x2_u*>(a.addend + static_cast<size_t>(m < a.M ? m : a.M - 1) * a.lda + nc), av);
+                        unpack4a(*reinterpret_cast<const u32x2_u*>(a.addend + static_cast<size_t>(m < a.M ? m : a.M - 1) * a.lda + nc), av);
                         if (!mul_add) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r) f[r] += av[r];
@@ -1998,8 +2031,11 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                         for (int r = 0; r < 4; ++r) f[r] *= av[r];
                     }
                     u32x2 o;
-                    o.x = static_cast<uint32_t>(f2h(f[0])) | (static_cast<uint32_t>(f2h(f[1])) << 16);
-                    o.y = static_cast<uint32_t>(f2h(f[2])) | (static_cast<uint32_t>(f2h(f[3])) << 16);
+                    if constexpr (BF) { o.x = wr_cvt_pk<true>(f[0], f[1]); o.y = wr_cvt_pk<true>(f[2], f[3]); }
+                    else {
+                        o.x = static_cast<uint32_t>(f2h(f[0])) | (static_cast<uint32_t>(f2h(f[1])) << 16);
+                        o.y = static_cast<uint32_t>(f2h(f[2])) | (static_cast<uint32_t>(f2h(f[3])) << 16);
+                    }
                     if (OPT && has_amax) {
                         typedef unsigned short us2 __attribute__((ext_vector_type(2)));
                         const us2 m = __builtin_elementwise_max(__builtin_bit_cast(us2, o.x & keep_lo), __builtin_bit_cast(us2, o.y & keep_hi));
@@ -2105,6 +2141,31 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
 #endif
 }
 
+constexpr int WR_SMALL = 14;                           // (index of the 32 x 64 small-batch tiling in g_wr below)
+
+#ifdef MIXQ_WR_BF16_TU
+// ---- the bf16 forms (this file compiled as gemm_wreg_bf16.hip) ---------------------------------------------------------
+// BF = true: bf16 x_out / w_out / addend / y.  Only what the automatic choice can return - the tilings of g_cost8 / g_cost6 plus WR_SMALL -
+// with the template arguments of the same rows of g_wr (whose geometry the launch reads).  No nibble form, no paired epilogue, no probes.
+struct WrBf16 { int cfg; void (*k8)(const WrArgs); void (*k6)(const WrArgs); };
+#define MIXQ_WRB8(C, MBv, WNBv, NS, Dv, LD) { C, gemm_wreg_kernel<MBv, WNBv, NS, Dv, 0, LD, 0, true>, nullptr }
+#define MIXQ_WRB(C, MBv, WNBv, NS, Dv, LD, NS6, D6) { C, gemm_wreg_kernel<MBv, WNBv, NS, Dv, 0, LD, 0, true>, gemm_wreg_kernel<MBv, WNBv, NS6, D6, 3, LD, 0, true> }
+const WrBf16 g_wr_bf16[] = {
+    MIXQ_WRB(0, 8, 3, 16, 4, 2, 8, 2), MIXQ_WRB(4, 8, 2, 16, 4, 2, 8, 2), MIXQ_WRB8(5, 8, 4, 16, 3, 2), MIXQ_WRB(6, 4, 2, 16, 4, 2, 12, 3),
+    MIXQ_WRB(7, 4, 3, 16, 4, 2, 12, 3), MIXQ_WRB(8, 4, 4, 16, 4, 2, 12, 3), MIXQ_WRB8(9, 8, 1, 8, 4, 1), MIXQ_WRB8(10, 4, 1, 8, 4, 1),
+    MIXQ_WRB(WR_SMALL, 2, 1, 8, 6, 1, 12, 4),
+};
+}  // namespace
+
+// the kernel (launch handle) of tiling c in its bf16 form, or nullptr: bit 8, or 6 (int4 as FP6 codes).  WrArgs is this file's struct in
+// either translation unit, so gemm_wreg.hip fills the argument block and launches the handle (mixq_wr_launch).
+const void* mixq_wr_bf16_kernel(int bit, int c)
+{
+    for (const auto& b : g_wr_bf16)
+        if (b.cfg == c) return reinterpret_cast<const void*>(bit == 8 ? b.k8 : (bit == 6 ? b.k6 : nullptr));
+    return nullptr;
+}
+#else
 // ---- configuration table -------------------------------------------------------------------------------------------
 struct WrConfig {
     const char* name;
@@ -2255,7 +2316,6 @@ const WrConfig g_wr[] = {
 #endif
 #endif
 };
-constexpr int WR_SMALL = 14;
 constexpr int WR_KSPLIT = 15;
 constexpr int NUM_WR = sizeof(g_wr) / sizeof(g_wr[0]);
 #ifdef MIXQ_TUNING
@@ -2321,6 +2381,19 @@ int mixq_wr_pick(int bit, int M, int N, int KB)
     if (cdiv(M, 32) * cdiv(N, 64) <= cus && cdiv(M, 64) * cdiv(N, 64) <= cus / 2) return WR_SMALL;
     return wr_cheapest(bit, M, N, KB, cus, [bit](int, const WrConfig& g) { return bit != 4 || g.k4 != nullptr; });   // (bit 4: tilings with a nibble form)
 }
+
+// The bf16 forms' choice: the same model over the tilings that have one; every batch size stays with these kernels (gemm_skinny.hip has no bf16
+// form: where fp16 streams a narrow layer's small batch through it, bf16 takes WR_SMALL).  -1: no tiling serves the problem - the caller answers
+// MIXQ_ESHAPE (wr_cheapest returns -1 when its filter admits nothing; that must never index g_wr).
+int mixq_wr_pick_bf16(int bit, int M, int N, int KB)
+{
+    if (bit != 8 && bit != 6) return -1;
+    if (M <= 32) return mixq_wr_bf16_kernel(bit, WR_SMALL) ? WR_SMALL : -1;
+    const int cus = mixq_num_cus();
+    if (bit == 8 && cdiv(M, 32) * cdiv(N, 64) <= cus && cdiv(M, 64) * cdiv(N, 64) <= cus / 2 && mixq_wr_bf16_kernel(8, WR_SMALL)) return WR_SMALL;   // (as mixq_wr_pick)
+    return wr_cheapest(bit, M, N, KB, cus, [bit](int c, const WrConfig&) { return mixq_wr_bf16_kernel(bit, c) != nullptr; });
+}
+bool mixq_wr_has_bf16(int bit, int c) { return c >= 0 && c < NUM_WR && mixq_wr_bf16_kernel(bit, c) != nullptr; }
 
 // The joint gate / up launch (N = the interleaved rows of both layers): the same model over the tilings that have the paired epilogue.
 int mixq_wr_pick_pair(int bit, int M, int N, int KB)
@@ -2405,9 +2478,10 @@ void mixq_wr_hint_next(const void* w, long long bytes) { t_next_w = static_cast<
 int mixq_wr_launch(int c, int bit, const void* q_x, const void* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
                    const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
                    const uint16_t* addend, int lda, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int KB, int act,
-                   unsigned long long* trace, hipStream_t st, uint32_t* row_amax, const uint32_t* amax_mask, int n_begin, int n_cols)
+                   unsigned long long* trace, hipStream_t st, uint32_t* row_amax, const uint32_t* amax_mask, int n_begin, int n_cols, bool bf16)
 {
     if (c < 0 || c >= NUM_WR) return MIXQ_EINVAL;
+    if (bf16 && (act == MIXQ_ACT_SILU_PAIR || !mixq_wr_bf16_kernel(bit, c))) return MIXQ_EINVAL;    // (no paired epilogue, no form outside gemm_wreg_bf16.hip's table)
     if (n_cols < 0) n_cols = N - n_begin;                                   // (the default: every weight row from n_begin on)
     if (n_begin < 0 || (n_begin & 63) || n_cols <= 0 || n_begin + n_cols > N) return MIXQ_EINVAL;
     const bool pair = act == MIXQ_ACT_SILU_PAIR;                            // (the paired epilogue is a kernel form, not a run-time switch)
@@ -2445,7 +2519,8 @@ int mixq_wr_launch(int c, int bit, const void* q_x, const void* q_w, const uint1
     if (t_fx && t_fq && t_fcnt && t_fK > 0 && (t_fK & 7) == 0 && n_begin == 0 && n_cols == N) { static const int ff = [] { const char* e = getenv("MIXQ_FUSE_FLAGS"); return e ? atoi(e) : 0; }(); a.fx = t_fx; a.fq = t_fq; a.fcnt = t_fcnt; a.fK = t_fK; a.fflags = ff; }
 #endif
     void (*k)(const WrArgs) = pair ? (bit == 8 ? g.k8p : g.k6p) : (bit == 8 ? g.k8 : (bit == 6 ? g.k6 : g.k4));
-    if (!k) return MIXQ_EINVAL;
+    const void* kh = bf16 ? mixq_wr_bf16_kernel(bit, c) : reinterpret_cast<const void*>(k);     // (the bf16 forms live in gemm_wreg_bf16.hip's code object)
+    if (!kh) return MIXQ_EINVAL;
     int units = a.tiles_m * a.tiles_n;
     if (c == WR_KSPLIT) {
         if (n_begin || n_cols != N) return MIXQ_EINVAL;
@@ -2462,7 +2537,13 @@ int mixq_wr_launch(int c, int bit, const void* q_x, const void* q_w, const uint1
 #else
     const size_t shm = ring > stg ? ring : stg;
 #endif
-    if (int rc = mixq_ensure_dynamic_lds(reinterpret_cast<const void*>(k), shm)) return rc;
-    hipLaunchKernelGGL(k, dim3(units), dim3((WR_CW + g.loaders) * 64), shm, st, a);
+    if (int rc = mixq_ensure_dynamic_lds(kh, shm)) return rc;
+    if (bf16) {
+        void* params[] = {&a};
+        if (hipError_t e = hipLaunchKernel(kh, dim3(units), dim3((WR_CW + g.loaders) * 64), params, shm, st)) return static_cast<int>(e);
+    } else {
+        hipLaunchKernelGGL(k, dim3(units), dim3((WR_CW + g.loaders) * 64), shm, st, a);
+    }
     return mixq_launch_status();
 }
+#endif  // MIXQ_WR_BF16_TU

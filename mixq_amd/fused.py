@@ -35,6 +35,14 @@ def split_pair_rows(joint: torch.Tensor):
     return v[:, 0].reshape(N2 // 2, *rest), v[:, 1].reshape(N2 // 2, *rest)
 
 
+def _refuse_bf16(config, who):
+    """The fused RMSNorm and MixLlamaMLP's fused routes exist in float16 only: under a bfloat16 model (MixqConfig.act_dtype) they say so
+    instead of detouring through float16."""
+    if getattr(config, "act_dtype", torch.float16) == torch.bfloat16:
+        raise NotImplementedError(f"{who} has no bfloat16 form yet (the fused RMSNorm, the joint gate / up launch and MixLlamaMLP's fused "
+                                  f"routes are float16 only); under act_dtype=torch.bfloat16 call the MixLinear_GEMM layers themselves")
+
+
 class FasterTransformerRMSNorm(nn.Module):
     def __init__(self, weight, eps=1e-6, cache=None):
         super().__init__()
@@ -42,11 +50,13 @@ class FasterTransformerRMSNorm(nn.Module):
         self.variance_epsilon = eps
         self.cache = cache
         self.next_layer = None
+        _refuse_bf16(getattr(cache, "config", None), "FasterTransformerRMSNorm")     # (known here when the cache carries the model's config)
 
     @torch.no_grad()
     def forward(self, x):
-        output = torch.empty_like(x)
         nl = self.next_layer
+        _refuse_bf16(getattr(nl, "config", None) or getattr(self.cache, "config", None), "FasterTransformerRMSNorm")
+        output = torch.empty_like(x)
         if nl is None:
             _backend.layernorm_forward_cuda(x, self.weight, output, self.variance_epsilon)
             return output
@@ -97,6 +107,7 @@ class MixLlamaMLP(nn.Module):
         self.MLPCache = MixGemmCache
         # the model's switches: the cache's MixqConfig when there is one, else up_proj's (config.py)
         object.__setattr__(self, "config", getattr(MixGemmCache, "config", None) or getattr(up_proj, "config", None) or _L.MixqConfig())
+        _refuse_bf16(self.config, "MixLlamaMLP")
         # gate_proj and up_proj as ONE launch (MIXQ_ACT_SILU_PAIR): the interleaved operands, built at the first forward after both
         # layers' outlier predictions froze.  A plain attribute, not a buffer: the state_dict stays the reference's (two q_weight tensors)
         object.__setattr__(self, "_joint", None)

@@ -61,11 +61,11 @@ def _pad16(n: int) -> int:
 
 
 class _ColStore:
-    """Growable [rows, cap] fp16 storage whose first n columns are live; row stride stays a multiple of 16 elements
-    so the GEMM's fp16 MFMA tail can read 16-byte fragments (include/mixq_hip.h: ldxo/ldwo)."""
+    """Growable [rows, cap] 16-bit storage (fp16; bf16 for the activation outliers of a bf16 layer) whose first n columns are live; row
+    stride stays a multiple of 16 elements so the GEMM's 16-bit MFMA tail can read 16-byte fragments (include/mixq_hip.h: ldxo/ldwo)."""
 
-    def __init__(self, rows, device, init: Tensor | None = None):
-        self.rows, self.device = rows, device
+    def __init__(self, rows, device, init: Tensor | None = None, dtype=torch.float16):
+        self.rows, self.device, self.dtype = rows, device, dtype
         self.n = 0
         self.buf = None
         if init is not None and init.numel():
@@ -77,7 +77,7 @@ class _ColStore:
             return
         need = _pad16(self.n + k)
         if self.buf is None or self.buf.shape[1] < need:
-            nb = torch.zeros((self.rows, max(need, 32)), dtype=torch.float16, device=self.device)
+            nb = torch.zeros((self.rows, max(need, 32)), dtype=self.dtype, device=self.device)
             if self.buf is not None and self.n:
                 nb[:, :self.n] = self.buf[:, :self.n]
             self.buf = nb
@@ -91,13 +91,13 @@ class _ColStore:
 
 
 def _gemm_ready(t: Tensor | None) -> Tensor | None:
-    """Return `t` (a [R,n] fp16 matrix) in a layout the GEMM tail accepts: row stride >= pad16(n), multiple of 8."""
+    """Return `t` (a [R,n] fp16 or bf16 matrix) in a layout the GEMM tail accepts: row stride >= pad16(n), multiple of 8."""
     if t is None or t.shape[1] == 0:
         return None
     n = t.shape[1]
     if t.stride(1) == 1 and t.stride(0) >= _pad16(n) and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0:
         return t
-    buf = torch.zeros((t.shape[0], _pad16(n)), dtype=torch.float16, device=t.device)
+    buf = torch.zeros((t.shape[0], _pad16(n)), dtype=t.dtype, device=t.device)
     buf[:, :n] = t
     return buf[:, :n]
 
@@ -106,7 +106,8 @@ class _Derived:
     """Everything a layer DERIVES from its state (weights, `ind`, `weight_cache`, device) and keeps between forwards, in one place:
 
       wpk / wpk_small   the packed weight image(s) the GEMM streams (after compaction `wpk` is the layer's ONLY copy of the weights)
-      wo_ready          `weight_cache` in the GEMM tail's padded layout
+      wo_ready          `weight_cache` in the GEMM tail's padded layout; for a bf16 layer its bf16 image RNE_bf16(weight_cache) (the tail's
+                        MFMA takes bf16 operands; the buffer itself, the state_dict and checkpoints stay fp16)
       ind_buf, n_dev    `ind` padded to a capacity + the live count in device memory
       cmask             bit-per-input-column mask of `ind` (a producer's row-maximum side output)
       amax_buf          int32 row maxima left by the GEMM that produced this layer's input; allocated ONCE at the cache's row capacity
@@ -197,6 +198,14 @@ class MixLinear_GEMM(nn.Module):
         self.bit = bit
         if bit not in (4, 8):
             raise ValueError("MixLinear_GEMM: bit must be 4 or 8")
+        # the model's activation dtype (config.py: act_dtype) - what bfloat16 does not serve is said here too, not by the first forward
+        act_dtype = getattr(getattr(cache, "config", None), "act_dtype", torch.float16)
+        if act_dtype == torch.bfloat16:
+            if weight_only:
+                raise ValueError("MixLinear_GEMM: weight_only (W8A16) layers have no bfloat16 form; use act_dtype=torch.float16")
+            if bit == 8 and in_features % 64:
+                raise ValueError(f"MixLinear_GEMM: a bfloat16 W8A8 layer needs in_features % 64 == 0 - there is no plain-operand bfloat16 GEMM "
+                                 f"(got {in_features} -> {out_features})")
         # the kernels' shape contract (include/mixq_hip.h): said here, where the layer is built, not by the first forward's MIXQ_ESHAPE
         if not weight_only and (in_features % (64 if bit == 8 else 128) or out_features % 4):
             raise ValueError(f"MixLinear_GEMM: W{bit}A{bit} needs in_features % {64 if bit == 8 else 128} == 0 and out_features % 4 == 0 "
@@ -261,6 +270,10 @@ class MixLinear_GEMM(nn.Module):
             return q
 
         W = linear.weight.data.to(dev)                      # a copy when it moves; cloned below before any in-place op
+        if W.dtype == torch.bfloat16 and q.config.act_dtype == torch.bfloat16:
+            # the reference's "in W's dtype" arithmetic would quantise in bfloat16 (8 significand bits for values up to 127): scale_col and
+            # the rounding are computed from the fp32 image of the bf16 weights instead.  An fp16 Linear takes the reference's path unchanged.
+            W = W.float()
         N = linear.out_features
         if bit == 8:
             # linear.py:113-119: scale = fp16(rowabsmax/127); q = round(W / scale) in W's dtype, cast to int8
@@ -307,7 +320,8 @@ class MixLinear_GEMM(nn.Module):
             self._wstore = _ColStore(self.out_features, weight_cache.device,
                                      self.weight_cache if (self.weight_cache is not None and self.ind.shape[0]) else None)
         xs = _ColStore(inputs.shape[0], inputs.device,
-                       cache.activation_outliers if (self.ind.shape[0] and cache.activation_outliers is not None) else None)
+                       cache.activation_outliers if (self.ind.shape[0] and cache.activation_outliers is not None) else None,
+                       dtype=activation_outliers.dtype)
         xs.append(activation_outliers)
         self._wstore.append(weight_cache)
         cache.activation_outliers = xs.view() if xs.n else activation_outliers
@@ -523,6 +537,22 @@ class MixLinear_GEMM(nn.Module):
         self._amax_dirty = True
         return self._amax_buf, self._col_mask()
 
+    @property
+    def act_dtype(self):
+        """The dtype this layer takes x in and returns y in: its model's (config.py: MixqConfig.act_dtype)."""
+        return self.config.act_dtype
+
+    def _wo_operand(self):
+        """`weight_cache` as the GEMM tail's weight operand: padded rows; for a bf16 layer the bf16 image RNE_bf16(weight_cache) - ONE
+        rounding of the fp16 buffer, derived state that is never saved.  weight_cache is static between outlier appends: built once per
+        (buffer identity, version, dtype), not on every forward (e.g. a [N,129] buffer loaded from a checkpoint)."""
+        wc = self.weight_cache
+        dt = self.act_dtype
+        key = (id(wc), wc.data_ptr(), wc._version, tuple(wc.shape), wc.stride(0), dt)
+        if self._wo_key != key:
+            self._wo_ready, self._wo_key = _gemm_ready(wc if wc.dtype == dt else wc.to(dt)), key
+        return self._wo_ready
+
     def _gemm(self, cache, M, act, addend=None, row_amax=None, col_mask=None):
         n = int(self.ind.shape[0])
         xo = wo = n_dev = None
@@ -534,11 +564,7 @@ class MixLinear_GEMM(nn.Module):
             xo = _gemm_ready(xo)
             # weight_cache is static between outlier appends: re-pad it (e.g. a [N,129] buffer loaded from a checkpoint)
             # once, not on every forward
-            wc = self.weight_cache
-            key = (id(wc), wc.data_ptr(), wc._version, tuple(wc.shape), wc.stride(0))
-            if self._wo_key != key:
-                self._wo_ready, self._wo_key = _gemm_ready(wc), key
-            wo = self._wo_ready
+            wo = self._wo_operand()
             if wo is None or wo.shape[1] != n:
                 raise RuntimeError("MixLinear_GEMM: outlier operands do not match `ind`")
             # capacity = the padded width both operands really have; the count itself is read from device memory
@@ -558,6 +584,8 @@ class MixLinear_GEMM(nn.Module):
             if want != FMT_PLAIN:
                 qx = _backend.PackOperand(qx[:M].contiguous(), want)
         extra = {} if row_amax is None else {"row_amax": row_amax, "col_mask": col_mask}
+        if self.act_dtype != torch.float16:
+            extra["dtype"] = self.act_dtype                  # (the _bf16 entry points: y, x_out, w_out and the addend in bfloat16)
         if n:
             return _backend.FusedLinear(qx, w, cache.x_scale, self.scale_col, _wide(xo, n_cap), _wide(wo, n_cap), n_cap, self.bias, M, self.out_features, self.in_features, bit=self.bit,
                                         act=act, addend=addend, n_out_dev=n_dev, **extra)
@@ -598,7 +626,7 @@ class MixLinear_GEMM(nn.Module):
                 id(b.get("scale_col"))) + d["config"].key()
 
     def _build_plan(self, cache, inputs, M):
-        if M == 0 or inputs.dtype != torch.float16 or inputs.stride(1) != 1 or inputs.stride(0) % 8:
+        if M == 0 or inputs.dtype != self.act_dtype or inputs.stride(1) != 1 or inputs.stride(0) % 8:
             return None
         wpk = self._packed_weight(M)
         if wpk is None:
@@ -607,17 +635,14 @@ class MixLinear_GEMM(nn.Module):
         ind_buf, n_dev = self._ind_dev()
         wo = None
         if n:
-            wc = self.weight_cache
-            key = (id(wc), wc.data_ptr(), wc._version, tuple(wc.shape), wc.stride(0))
-            if self._wo_key != key:
-                self._wo_ready, self._wo_key = _gemm_ready(wc), key
-            wo = self._wo_ready
+            wo = self._wo_operand()
             if wo is None or wo.shape[1] != n or wo.stride(0) < _pad16(n):
                 return None
             wo = _wide(wo, _pad16(n))
         # (frozen: `ind` never changes again, so the quantise pass gets the kept bit mask of its columns instead of building one per launch)
+        extra = {} if self.act_dtype == torch.float16 else {"dtype": self.act_dtype}      # (mixq_linear_forward_bf16)
         return _backend.ForwardPlan(M, self.out_features, self.in_features, self.bit, self._sigma_f, inputs.stride(0), ind_buf, n, n_dev,
-                                    cache.x_scale, wpk, self.scale_col, wo, self.bias, self.x_fmt(M), kept_mask=self._col_mask() if n else None)
+                                    cache.x_scale, wpk, self.scale_col, wo, self.bias, self.x_fmt(M), kept_mask=self._col_mask() if n else None, **extra)
 
     # ------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -627,13 +652,15 @@ class MixLinear_GEMM(nn.Module):
         cache.shape = x.shape[:-1] + (self.out_features,)
         inputs = x.reshape(-1, x.shape[-1])
         M = inputs.shape[0]
+        if self.act_dtype == torch.bfloat16 and inputs.dtype != torch.bfloat16:
+            raise RuntimeError("MixLinear_GEMM: x must be bfloat16 (this layer's model runs in bfloat16: MixqConfig.act_dtype)")
         if unfused and not self.add_outliers and self.weight_only is False and self.config.one_call_forward:
             # prediction frozen: extract + quantise + GEMM enqueued by one C call on a kept argument block; bit-identical to the
             # route below (tests/test_gpu_round3.py::test_one_call_forward_is_bit_identical)
             # The argument block takes x by ADDRESS: what the two-call route checked in QuantFused is checked here on every call - a
             # kept block must not be replayed on a bf16 / fp32 tensor, another column count or a strided last dimension
-            if inputs.dtype != torch.float16:
-                raise RuntimeError("MixLinear_GEMM: x must be float16")
+            if inputs.dtype != self.act_dtype:
+                raise RuntimeError(f"MixLinear_GEMM: x must be {str(self.act_dtype).replace('torch.', '')}")
             if inputs.shape[1] != self.in_features:
                 raise RuntimeError(f"MixLinear_GEMM: x has {inputs.shape[1]} columns, the layer {self.in_features} input features")
             if inputs.stride(1) != 1 and M:
@@ -725,6 +752,8 @@ class MixLinear_GEMM(nn.Module):
         layer's pre-pass row maxima (over the columns it does not extract), and its forward quantises in one pass instead of two."""
         inputs = x.reshape(-1, x.shape[-1])
         M = inputs.shape[0]
+        if inputs.dtype != self.act_dtype or (mul is not None and mul.dtype != self.act_dtype):
+            raise RuntimeError(f"MixLinear_GEMM: x and mul must be {str(self.act_dtype).replace('torch.', '')} (MixqConfig.act_dtype)")
         if not self.forward_without_precondition_len == cache.ind.shape[0]:
             if cache.ind.shape[0]:
                 ind = cache.new_ind
@@ -745,7 +774,9 @@ class MixLinear_GEMM(nn.Module):
         if amax_for is not None and self.bit == 8 and amax_for.in_features == self.out_features:
             wpk = self._packed_weight()
             if wpk is not None and \
-                    _backend.amax_supported(M, self.out_features, self.in_features, _fmt_of(cache.q_xcache), _fmt_of(wpk)):
+                    _backend.amax_supported(M, self.out_features, self.in_features, _fmt_of(cache.q_xcache), _fmt_of(wpk),
+                                            **({} if self.act_dtype == torch.float16 else {"dtype": self.act_dtype})) and \
+                    getattr(amax_for, "act_dtype", torch.float16) == self.act_dtype:
                 target = amax_for.amax_target(M, x.device)
         extra = {} if target is None else {"row_amax": target[0], "col_mask": target[1]}
         if mul is not None:

@@ -192,12 +192,14 @@ def _weight_for_gemm(q_w, bit):
 
 def _act_suffix(x, who):
     """Entry-point suffix of an activation tensor's 16-bit container: "" for float16 (the reference's), "_bf16" for bfloat16 (the
-    `_bf16` twins of include/mixq_hip.h: same arguments, x / x_out read and written as bfloat16, x_scale still fp16)."""
-    if x.dtype == torch.float16:
+    `_bf16` twins of include/mixq_hip.h: same arguments, x / x_out read and written as bfloat16, x_scale still fp16).  `x` may also be
+    the dtype itself (a layer's MixqConfig.act_dtype, where there is no 16-bit tensor to read it from)."""
+    dtype = x if isinstance(x, torch.dtype) else x.dtype
+    if dtype == torch.float16:
         return ""
-    if x.dtype == torch.bfloat16:
+    if dtype == torch.bfloat16:
         return "_bf16"
-    raise RuntimeError(f"{who}: x must be float16 or bfloat16, got {x.dtype}")
+    raise RuntimeError(f"{who}: x must be float16 or bfloat16, got {dtype}")
 
 
 def FindRowScale(x, x_scale, M, K, bit=8):
@@ -763,16 +765,28 @@ def DequantWeightCols(q_w, scale_col, ind, bit, out=None):
 PAIR_LAUNCH = True                       # FusedLinear serves ACT_SILU_PAIR (fused.MixLlamaMLP asks before taking its joint gate / up route)
 
 
-def amax_supported(M, N, K, x_fmt, w_fmt):
-    """True when the GEMM can leave the next layer's row maxima as a side output for this problem (mixq_gemm_amax_supported)."""
+def _check_same_dtype(dtype, who, **tensors):
+    """The 16-bit tensors of a GEMM call (x_out, w_out, addend, out) share ONE container, the layer's: no mixing, no silent conversion."""
+    for name, t in tensors.items():
+        if t is not None and t.dtype != dtype:
+            raise RuntimeError(f"{who}: {name} must be {dtype} like the call's other 16-bit tensors (dtype={dtype}), got {t.dtype}")
+
+
+def amax_supported(M, N, K, x_fmt, w_fmt, dtype=torch.float16):
+    """True when the GEMM can leave the next layer's row maxima as a side output for this problem (mixq_gemm_amax_supported; `dtype`: the
+    container of y - the bf16 forms serve every batch size)."""
     if x_fmt != FMT_P16X64 or w_fmt != FMT_F16X64:
         return False
-    return bool(_capi.load().mixq_gemm_amax_supported(M, N, K, X_PACKED | W_F16X64))
+    fn = getattr(_capi.load(), "mixq_gemm_amax_supported" + _act_suffix(dtype, "amax_supported"))
+    return bool(fn(M, N, K, X_PACKED | W_F16X64))
 
 
 def FusedLinear(q_x, q_w, x_scale, scale_col, x_out, w_out, n_out, bias, M, N, K, bit=8, act=ACT_NONE, n_out_dev=None,
-                addend=None, out=None, x_packed=None, w_packed=None, row_amax=None, col_mask=None):
+                addend=None, out=None, x_packed=None, w_packed=None, row_amax=None, col_mask=None, dtype=torch.float16):
     """(iii)+(iv): int8/int4 MFMA GEMM + dequant + fp16 outlier correction + addend + act + bias -> fp16 [M,N].
+    `dtype` (float16, or bfloat16: the `_bf16` entry points) is the container of x_out, w_out, addend and y - with no outlier columns, no
+    addend and no `out` there is no 16-bit tensor to read it from, so it is said; the tensors that are present must agree with it.
+    x_scale, scale_col and bias are float16 in either form.
     The operand layouts come from the tensors' own format tags (set_fmt / the packing and quantising functions above);
     x_packed / w_packed = True/False force P16x64 / plain for untagged buffers.  `n_out_dev` (device int32[1]) overrides the
     outlier count: n_out then is the capacity of x_out / w_out (columns >= the device count are ignored, whatever they hold).
@@ -787,8 +801,13 @@ def FusedLinear(q_x, q_w, x_scale, scale_col, x_out, w_out, n_out, bias, M, N, K
     # (ACT_SILU_PAIR: N counts the interleaved gate / up rows, the product has N / 2 columns)
     if act == ACT_SILU_PAIR and (N % 16 or not _is_zero_addend(addend)):
         raise RuntimeError("FusedLinear: ACT_SILU_PAIR needs N % 16 == 0 and takes no addend")
-    y = out if out is not None else torch.empty((M, N // 2 if act == ACT_SILU_PAIR else N), dtype=torch.float16, device=q_x.device)
+    sfx = _act_suffix(dtype, "FusedLinear")
+    if sfx and act == ACT_SILU_PAIR:
+        raise RuntimeError("FusedLinear: ACT_SILU_PAIR (the joint gate / up launch) has no bfloat16 form")
+    y = out if out is not None else torch.empty((M, N // 2 if act == ACT_SILU_PAIR else N), dtype=dtype, device=q_x.device)
+    _check_same_dtype(dtype, "FusedLinear", out=out)
     if n_out and x_out is not None and w_out is not None:
+        _check_same_dtype(dtype, "FusedLinear", x_out=x_out, w_out=w_out)
         xop, ldxo = _rows(x_out, "x_out")
         wop, ldwo = _rows(w_out, "w_out")
     else:
@@ -799,6 +818,7 @@ def FusedLinear(q_x, q_w, x_scale, scale_col, x_out, w_out, n_out, bias, M, N, K
         if addend is None:
             raise RuntimeError("FusedLinear: ACT_SILU_MUL needs the multiplier in `addend`")
         _dev_check(addend)
+        _check_same_dtype(dtype, "FusedLinear", addend=addend)
         ap, lda = _rows(addend, "addend")
     elif _is_zero_addend(addend):
         ap, lda = None, 0
@@ -806,15 +826,16 @@ def FusedLinear(q_x, q_w, x_scale, scale_col, x_out, w_out, n_out, bias, M, N, K
         if isinstance(addend, PendingOutlierProduct):
             addend._materialize()
         _dev_check(addend)
+        _check_same_dtype(dtype, "FusedLinear", addend=addend)
         ap, lda = _rows(addend, "addend")
     if row_amax is not None:
         if bit != 8 or row_amax.numel() < M or row_amax.element_size() != 4:
             raise RuntimeError("FusedLinear: row_amax needs an int8 GEMM and a 4-byte buffer of at least M entries")
-        _capi.call("mixq_gemm_i8_fused_amax", q_x.data_ptr(), q_w.data_ptr(), x_scale.data_ptr(), scale_col.data_ptr(), xop, ldxo, wop, ldwo,
+        _capi.call("mixq_gemm_i8_fused_amax" + sfx, q_x.data_ptr(), q_w.data_ptr(), x_scale.data_ptr(), scale_col.data_ptr(), xop, ldxo, wop, ldwo,
                    n_out, _ptr(n_out_dev), ap, lda, _ptr(bias), y.data_ptr(), y.stride(0), M, N, K, act, _layout_bits(x_fmt, w_fmt),
                    row_amax.data_ptr(), _ptr(col_mask), _stream())
         return y
-    fn = "mixq_gemm_i8_fused" if bit == 8 else "mixq_gemm_i4_fused"
+    fn = ("mixq_gemm_i8_fused" if bit == 8 else "mixq_gemm_i4_fused") + sfx
     _capi.call(fn, q_x.data_ptr(), q_w.data_ptr(), x_scale.data_ptr(), scale_col.data_ptr(), xop, ldxo, wop, ldwo, n_out,
                _ptr(n_out_dev), ap, lda, _ptr(bias), y.data_ptr(), y.stride(0), M, N, K, act, _layout_bits(x_fmt, w_fmt), _stream())
     return y
@@ -825,10 +846,12 @@ class ForwardPlan:
     a forward then costs three allocations, four pointer updates and ONE foreign call that enqueues the quantise pass and the
     GEMM (the steady state of linear.py:187-193 + :244-285).  Holds references to every tensor whose address it carries."""
 
-    __slots__ = ("args", "ref", "fn", "keep", "M", "N", "K", "ldx", "n", "ldxo", "q_shape", "q_dtype", "qfmt", "device", "lock", "captured", "kept_mask")
+    __slots__ = ("args", "ref", "fn", "keep", "M", "N", "K", "ldx", "n", "ldxo", "q_shape", "q_dtype", "qfmt", "device", "lock", "captured", "kept_mask", "dtype", "fn_name")
 
-    def __init__(self, M, N, K, bit, sigma, ldx, ind_buf, n, n_dev, x_scale, q_w, scale_col, w_out, bias, qfmt, act=ACT_NONE, kept_mask=None):
+    def __init__(self, M, N, K, bit, sigma, ldx, ind_buf, n, n_dev, x_scale, q_w, scale_col, w_out, bias, qfmt, act=ACT_NONE, kept_mask=None, dtype=torch.float16):
         import ctypes as C
+        # dtype: the container of x, x_out, w_out and y (float16, or bfloat16: mixq_linear_forward_bf16); checked against x on every run
+        self.dtype, self.fn_name = dtype, "mixq_linear_forward" + _act_suffix(dtype, "ForwardPlan")
         _dev_check(x_scale, q_w, scale_col, ind_buf, n_dev, w_out, bias)
         if x_scale.numel() < M or scale_col.numel() < N:
             raise RuntimeError("ForwardPlan: x_scale / scale_col are shorter than M / N")
@@ -842,12 +865,13 @@ class ForwardPlan:
         a.x_scale, a.q_w, a.scale_col, a.bias = x_scale.data_ptr(), q_w.data_ptr(), scale_col.data_ptr(), _ptr(bias)
         self.ldxo = a.ldxo = _pad16(n_cap) if n_cap else 0
         if n_cap:
+            _check_same_dtype(dtype, "ForwardPlan", w_out=w_out)
             wop, ldwo = _rows(w_out, "w_out")
             if ldwo < n_cap or ldwo % 8:
                 raise RuntimeError("ForwardPlan: w_out row stride must be >= the outlier capacity and a multiple of 8")
             a.w_out, a.ldwo = wop, ldwo
         a.ldy = N
-        self.args, self.ref, self.fn = a, C.byref(a), _capi.load().mixq_linear_forward
+        self.args, self.ref, self.fn = a, C.byref(a), getattr(_capi.load(), self.fn_name)
         # kept_mask: the layer's kept outlier map of `ind` (include/mixq_hip.h: bits, count, AND-masks): the quantise pass then needs one memory round trip
         if kept_mask is not None:
             _dev_check(kept_mask)
@@ -861,7 +885,7 @@ class ForwardPlan:
         self.q_shape, self.q_dtype = (packed_rows(M) if qfmt else M, _q_row_bytes(K, bit, qfmt)), (torch.int8 if bit == 8 else torch.uint8)
 
     def run(self, x, row_amax=None, col_mask=None):
-        """x: fp16 [M,K] with the row stride the plan was built for.  Returns (y [M,N], q_x, x_out [M,n] or None).
+        """x: [M,K] in the plan's dtype with the row stride the plan was built for.  Returns (y [M,N], q_x, x_out [M,n] or None).
         row_amax (int32 [>= M] on the device): the rows' masked maxima left by the GEMM that produced x (FusedLinear(row_amax=...));
         the quantise pass is then the one-pass known-maximum kernel, which also clears the buffer."""
         dev = self.device
@@ -871,12 +895,12 @@ class ForwardPlan:
         # the block carries x by address: the same checks on every call as the two-call route's QuantFused
         if x.device != dev:
             raise RuntimeError(f"ForwardPlan: x lives on {x.device}, the plan was built for {dev}")
-        if x.dtype != torch.float16 or x.dim() != 2 or x.shape[0] != self.M or x.shape[1] != self.K or x.stride(1) != 1 or x.stride(0) != self.ldx:
-            raise RuntimeError(f"ForwardPlan: x must be float16 [{self.M}, {self.K}] with row stride {self.ldx} and a contiguous last dimension "
+        if x.dtype != self.dtype or x.dim() != 2 or x.shape[0] != self.M or x.shape[1] != self.K or x.stride(1) != 1 or x.stride(0) != self.ldx:
+            raise RuntimeError(f"ForwardPlan: x must be {str(self.dtype).replace('torch.', '')} [{self.M}, {self.K}] with row stride {self.ldx} and a contiguous last dimension "
                                f"(got {x.dtype} {tuple(x.shape)} strides {tuple(x.stride())})")
         q = torch.empty(self.q_shape, dtype=self.q_dtype, device=dev)
-        y = torch.empty((self.M, self.N), dtype=torch.float16, device=dev)
-        xo = torch.empty((self.M, self.ldxo), dtype=torch.float16, device=dev) if self.ldxo else None
+        y = torch.empty((self.M, self.N), dtype=self.dtype, device=dev)
+        xo = torch.empty((self.M, self.ldxo), dtype=self.dtype, device=dev) if self.ldxo else None
         if not self.captured and torch.cuda.is_current_stream_capturing():
             self.captured = True
         a = self.args
@@ -890,7 +914,7 @@ class ForwardPlan:
             a.x, a.q_x, a.y = x.data_ptr(), q.data_ptr(), y.data_ptr()
             rc = self.fn(self.ref, torch.cuda.current_stream(dev).cuda_stream)
         if rc != 0:
-            raise _capi.MixqError("mixq_linear_forward", rc)
+            raise _capi.MixqError(self.fn_name, rc)
         q._mixq_fmt = self.qfmt
         return y, q, (xo[:, :self.n] if xo is not None else None)
 

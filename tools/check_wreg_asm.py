@@ -7,10 +7,14 @@ scratch_* naming it.  (MFMAs read them legitimately, behind the s_waitcnt statem
 import os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# (source file, kernel name, how to read the template arguments out of the mangled name)
+# (source file, kernel name, how to read the template arguments out of the mangled name, ..., the file name it is checked under)
+WREG_ARGS = r"ILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E(?:Lb([01])E)?"
 TARGETS = [
-    ("gemm_wreg.hip", "gemm_wreg_kernel", r"ILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)", "MB={0} WNB={1} NSTAGE={2} D={3} Q={4} L={5} ABL={6}", 6),
-    ("gemm_w8a16.hip", "gemm_w8a16_kernel", r"ILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)", "w8a16 MB={0} WNB={1} NSTAGE={2} D={3} L={4} ABL={5}", 5),
+    ("gemm_wreg.hip", "gemm_wreg_kernel", WREG_ARGS, "MB={0} WNB={1} NSTAGE={2} D={3} Q={4} L={5} ABL={6}", 6, "gemm_wreg.hip"),
+    # gemm_wreg.hip compiled a second time, the bf16 forms: the container is the EIGHTH template argument (`bool BF`, Lb1E in the mangled
+    # name).  Their lines carry a leading "bf16 " tag, the fields and the checks are the same
+    ("gemm_wreg_bf16.hip", "gemm_wreg_kernel", WREG_ARGS, "MB={0} WNB={1} NSTAGE={2} D={3} Q={4} L={5} ABL={6}", 6, "gemm_wreg.hip"),
+    ("gemm_w8a16.hip", "gemm_w8a16_kernel", r"ILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)", "w8a16 MB={0} WNB={1} NSTAGE={2} D={3} L={4} ABL={5}", 5, "gemm_w8a16.hip"),
 ]
 
 
@@ -29,8 +33,8 @@ def regs(tok):
 def main():
     bad = 0
     only = set(sys.argv[1:])                                  # optional: source file names to restrict the check to
-    for fname, kname, tag_re, tag_fmt, abl_idx in TARGETS:
-        if only and fname not in only:
+    for fname, kname, tag_re, tag_fmt, abl_idx, under in TARGETS:
+        if only and under not in only:
             continue
         bad += check(fname, kname, tag_re, tag_fmt, abl_idx)
     return 1 if bad else 0
@@ -125,7 +129,8 @@ def check(fname, kname, tag_re, tag_fmt, abl_idx):
         sc = re.search(r"; ScratchSize: (\d+)", body)
         tag = re.search(tag_re, name).groups()
         abl = tag[abl_idx] != "0"
-        print(f"{tag_fmt.format(*tag)}: ring registers {len(loaded)}, in-flight LDS copies {len(lds_hits)}, "
+        bf16 = len(tag) > abl_idx + 1 and tag[abl_idx + 1] == "1"
+        print(f"{'bf16 ' if bf16 else ''}{tag_fmt.format(*tag)}: ring registers {len(loaded)}, in-flight LDS copies {len(lds_hits)}, "
               f"suspicious {len(hits)}" + ("  (ablation build: ignored)" if abl and hits else "") +
               (f"  [note: {len(notes)} scratch access(es) inside the counted region]" if notes else ""))
         for i, t in hits[:6]:
