@@ -59,15 +59,6 @@ struct WrArgs {
     // pairwise split-K (ABL = 50): one int32 slot of BM x BN per tile and one flag word per tile (zero between launches)
     uint8_t* ks_slots;
     unsigned int* ks_flags;
-#ifdef MIXQ_TUNING
-    // cross-layer prefetch experiment (round 6, mixq_gemm_hint_next_weights; measured negative, see the loader): the NEXT launch's weight image
-    const uint8_t* pf;
-    unsigned int pf_lines;                            // 128-byte lines of it
-    int pf_mode;                                      // bit 0: scalar-cache touches, bit 1: vector touches (one lane per line), bit 2: ... with the nt hint
-    // one-launch probe (ABL 77, mixq_gemm_set_fuse_probe): a stand-in quantise phase in front of the GEMM - fp16 rows in, bytes out, a counter per M tile
-    const uint16_t* fx; uint8_t* fq; unsigned int* fcnt; int fK;
-    int fflags;                                       // (probe breakdown, env MIXQ_FUSE_FLAGS: 1 no stores, 2 no drain, 4 no atomic add, 8 no poll, 16 ordinary instead of write-through stores)
-#endif
 };
 
 constexpr int WR_CW = 4;
@@ -106,11 +97,13 @@ template <int I, int N, class F> __device__ __forceinline__ void wr_static_for(F
 }
 
 // MB: 16-row activation blocks per tile (BM = 16 MB), WNB: 16-row weight blocks per wave (BN = 64 WNB), NSTAGE: X ring depth,
-// D: weight register ring depth (k-steps), Q: operand coding (0 int8; 1 nibble-packed int4, expanded to int8 in registers; 2 int4
-// carried as FP6 codes on the FP6 matrix pipe, MIXQ_FMT_F6X128 operands, k-steps of 128 elements), LOADERS: DMA waves, ABL (tuning): 0 normal,
-// 1 no weight loads, 2 no X traffic (no DMA, no LDS reads), 3 MFMA only, 4 weight loads issued but never waited for, 5 the loader
-// never waits for its DMA, 6 no k-loop barriers (4-6: timing probes, results are garbage), 7 no stores of Y, 8 ordinary instead of
-// nt stores, 9 return at entry, 12 no prologue ramp in the loader.
+// D: weight register ring depth (k-steps), Q: operand coding (0 int8; 1 nibble-packed int4, expanded to int8 in registers; 3 int4
+// carried as FP6 codes on the FP6 matrix pipe, MIXQ_FMT_F6X128 operands, k-steps of 128 elements), LOADERS: DMA waves (at least one),
+// ABL: 0 the shipped loop, 90 the paired gate / up epilogue on it (both: product).  Tuning build only: 50 pairwise split-K; 60 the first
+// form of the epilogue (the one split-K runs; the A/B partner of EPI2); the feed ablations 1 no weight loads, 2 no X traffic (no DMA, no LDS
+// reads), 3 MFMA only - int8 and FP6 tuple-ring forms, results are garbage - and 16 / 17 / 18: 3 / 2 / 1 with pseudo-random stand-in
+// operands; 7 no stores of Y; 9 return at entry; 36, 100 + 32 and 100 + 32 + 64 the in-k-step timeline (tools/trace_kstep.py).
+// The probes that stood beside these are closed and removed: NOTEBOOK.md, "Retired probes", has each one's answer and its profile.
 constexpr int MIXQ_Y_ST = 2;                // cache policy of the stores of Y (buffer-store aux bits): 2 = nt (streaming), 16 = sc1 (write-through), 18 = both, 0 = ordinary
 constexpr int MIXQ_Y_WT_MB = 4;             // tiles of at most this many 16-row blocks store Y write-through (sc1 | nt): the layers they serve write a few MB of Y in ONE round of
                                             // tiles, and lines written through during the epilogue are not left for the kernel's closing release to write back: -0.1 ... -0.25 us per launch at
@@ -137,14 +130,13 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
     // (ABL 16 / 17 / 18: the feed ablations 3 / 2 / 1 with PSEUDO-RANDOM bytes in the operands that are never loaded - the MFMA's power, hence the clock of a
     // power-limited launch, depends on how its operands switch: lane-constant stand-ins flatter every ablation; profiles/r05_ablations_random_operands.txt)
     constexpr bool RNDOPS = ABL >= 16 && ABL <= 18;
-    // ABL in [100, 228): the SHIPPED loop with probe features switched on bit by bit (tuning build; results are correct): FL bit 0 the FP6
-    // form's activation window holds all MB tuples, bit 1 the loaders sleep 64 cycles behind every DMA piece, bit 2 the loaders sleep 192 cycles
-    // in front of a stage's pieces, bit 3 loaders at priority 0, bit 4 consumers at priority 3, bit 5 the in-k-step timeline (as ABL 36),
-    // bit 6 ... stamped by consumer wave 2 (a SIMD no loader wave shares) instead of wave 0
-    constexpr int FL = (ABL >= 100 && ABL < 1124) ? ABL - 100 : 0;                 // (bit 7: the FP6 form's LDS image of rounds 3-5, see OLDSWZ)
+    // ABL = 100 + FL: the SHIPPED loop with the in-k-step timeline switched on (tuning build; results are correct).  FL is left with its two
+    // timeline bits: bit 5 (32) the timeline itself (as ABL 36), bit 6 (64) ... stamped by consumer wave 2 (a SIMD no loader wave shares)
+    // instead of wave 0
+    constexpr int FL = ABL >= 100 ? ABL - 100 : 0;
+    static_assert((FL & ~(32 | 64)) == 0 && (FL == 0 || (FL & 32)), "FL: bit 5 the timeline, bit 6 its stamping wave");
     constexpr int ABLK = ABL == 90 ? 0 : (RNDOPS ? 19 - ABL : (ABL >= 100 ? 0 : ABL));
     constexpr bool TL = ABL == 36 || (FL & 32);
-    constexpr bool WPROBE = ABLK == 76;                                            // (timing probe: the weights through LDS - see the loader's stage())
     constexpr int TLW = (FL & 64) ? 2 : 0;
     constexpr int CW = WR_CW;
     constexpr int NT = (CW + LOADERS) * 64;
@@ -159,23 +151,24 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
     // fragment's dwordx4 + dwordx2 are two outputs of one asm statement that are concatenated into the tuple right there - a pure
     // renaming IF the register coalescer assigns the outputs to the tuple's sub-registers (it does: no v_mov in the loop, checked on the
     // ISA by tools/check_wreg_asm.py and by the bit-exact tests - a copy at that point would read registers whose loads are in flight).
-    // That removes the 9 v_mov_b64 + wait states in front of each k-step's first MFMA of the Q = 2 form.  Loads are unconditional
+    // That removes the 9 v_mov_b64 + wait states in front of each k-step's first MFMA of the first FP6 form (Q = 2, retired: 22.1 against 20.9 us at the metric shape).  Loads are unconditional
     // (requests past the end of K wrap around to the first k-steps: valid addresses, never consumed, drained behind the loop), so
     // every wait is a compile-time count.
     constexpr bool I4 = Q == 1, F6 = Q >= 2, F6R = Q == 3;
+    static_assert(Q == 0 || Q == 1 || Q == 3, "operand codings: int8, nibble-packed int4, int4 as FP6 codes in a tuple ring");
     // WRAP: every k-step requests weights unconditionally - past the end of K the requests wrap around to the first k-steps (valid
     // addresses, never consumed, drained behind the loop) - so the last D + NSLOT k-steps need no conditional loads and no run-time wait
     // tables.  The tuple-ring FP6 form and the int8 form of the shipped loop: -0.8 ... -3.2 % over the BASELINE shapes between two product
     // builds (-1.3 % at the metric shape; profiles/r03_ab_wrap_tail.txt).
-    constexpr bool WRAP = F6R || ABLK == 41 || (Q == 0 && (ABLK == 0 || ABLK == 6 || (ABLK >= 60 && ABLK < 80)) && LOADERS != 0);
+    constexpr bool WRAP = F6R || (Q == 0 && (ABLK == 0 || ABLK == 60) && LOADERS != 0);
     constexpr int BLK = F6 ? 1536 : 1024;                // bytes of one 16-row operand block of one k-step
     constexpr int STAGE_BYTES = MB * BLK;
     constexpr int LOOK = NSTAGE - 2, NEWER = LOOK - 1;
-    // SELF (LOADERS = 0, the prefill form): four FAT waves, one per SIMD with the whole 512-entry register file each (256 accumulator
-    // registers at MB x WNB = 16 x 4: a 256 x 256 tile), and no room for loader waves - a fifth wave would halve every wave's register
-    // budget - so each consumer wave issues its quarter of the activation DMA itself, between its MFMAs.
-    constexpr bool SELF = LOADERS == 0;
-    constexpr int ISSUERS = SELF ? CW : LOADERS;
+    // (Round 3 also had a form without loader waves - 256 x 256 tiles, four fat waves that issued the activation DMA themselves between their
+    // MFMAs: 186.1 against 191.3 us for 128 x 256 at 4096 x 11008 x 4096 without outlier columns, 33 us of tail with 41, and a memory access
+    // violation at M = 8192; profiles/r03_prefill_ab.txt.  Removed.)
+    static_assert(LOADERS >= 1, "the activation DMA is issued by dedicated loader waves");
+    constexpr int ISSUERS = LOADERS;
     constexpr int LOADS = STAGE_BYTES / 1024 / ISSUERS;  // 1 KiB DMA pieces per issuing wave and stage
     constexpr int TLOADS = MB / ISSUERS;                 // the fp16 tail's X_out blocks per issuing wave
     constexpr int WL = F6 ? 2 * WNB : WNB;               // load instructions of one k-step's weight fragments (per wave)
@@ -188,11 +181,11 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
     constexpr bool PAIR = ABL == 90;
     constexpr int BNO = PAIR ? BN / 2 : BN;              // output columns of the staged tile
     constexpr int OPITCH = BNO * 2 + 16;
-    constexpr bool PREBIAS = !SELF && (MB * WNB * 4 + (D + 1) * WNB * (F6 ? 6 : 4) * (I4 ? 2 : 1) + MB * (F6 ? 6 : 4) + 40 <= 232);   // registers to spare for the bias prefetch
+    constexpr bool PREBIAS = (MB * WNB * 4 + (D + 1) * WNB * (F6 ? 6 : 4) * (I4 ? 2 : 1) + MB * (F6 ? 6 : 4) + 40 <= 232);   // registers to spare for the bias prefetch
     constexpr int AMAX_OFF = (BM * OPITCH + 15) & ~15;   // LDS: [CW][4][BM] row maxima (one slot per wave and lane group), behind the staging tile
     // tail k-steps (32 outlier columns each) whose X_out blocks go through LDS: two; four in the FP6 form - 4-bit layers carry 128
     // static fp16 columns (linear.py:100, fp_features_num), and k-steps beyond TQ cost every wave a global round trip for the same rows
-    constexpr int TQ = SELF ? 0 : (F6 ? 4 : 2);
+    constexpr int TQ = F6 ? 4 : 2;
     constexpr int TAILX = NSTAGE * STAGE_BYTES;          // LDS offset of those blocks: behind the ring, [TQ][MB] x 1 KiB
     // EPI2 (round 4): the epilogue as a pipeline of ROW PANELS (PJ = 2 blocks = 32 token rows each).  A consumer wave dequantises panel
     // p+1 between the fp16 tail MFMAs of panel p (the VALU work hides the MFMAs' latency and the other way round; the first form ran
@@ -201,7 +194,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
     // set reads the panel complete - no wait, no barrier on the producing side); the LOADER waves - idle since their last DMA - poll the
     // flags and copy staged panels out to Y with 16-byte nt row stores while the consumers work on the next panels, so only the last
     // panels' stores (shared by all six waves behind the one closing barrier) are exposed behind the arithmetic.
-    // Same operations per element in the same order as the first form (kept for the fat prefill tile, the pairwise split-K form and as
+    // Same operations per element in the same order as the first form (kept for the pairwise split-K form and as
     // the tuning build's A/B partner, ABLK 60): bit-identical (tests/test_gpu_round4.py).
     constexpr int PJ = MB >= 2 ? 2 : 1, NPAN = MB / PJ, PROWS = PJ * 16;
     // panels the loader waves copy out on their own (the rest is shared by all waves behind the final barrier: the path to memory takes
@@ -209,21 +202,20 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
     // (Tried and dropped, profiles/r04_ab_direct_stores.txt: no staging at all - block pairs exchanged between lanes with v_permlane16_swap so
     // that a lane holds 16 contiguous bytes, stored straight from registers as 64- / 32-byte row segments.  Bit-identical, 28.6 vs 24.6 us:
     // the memory system chokes on partial-line writes; full 384-byte row segments out of LDS are what it takes.)
-    constexpr int LP = (SELF || NPAN < 3) ? 0 : (ABLK == 61 ? 0 : (ABLK == 67 ? NPAN - 1 : NPAN - 2));   // (NPAN - 1, probe 67: the consumers end up waiting for the loaders: 24.14 vs 23.94 us)
+    constexpr int LP = NPAN < 3 ? 0 : NPAN - 2;
     constexpr int FLAG_OFF = TAILX + TQ * MB * 1024;     // LDS: "panel p staged by consumer wave w" words [NPAN][CW], behind the tail's X_out blocks
     // EPI2: the epilogue's scales (x_scale of the tile's rows, scale_col and bias of its columns) do not ride through the k loop in the
     // consumers' registers (20 VGPRs of the 128 x 192 tile, 14 requests and their address arithmetic in front of its second weight
     // request): a loader wave brings them into LDS by 16-bit LDS-DMA - one dword slot per element, zero-extended; rows past M and columns
     // past N read as zero through the buffer descriptor's range check - while the main loop runs, and the epilogue reads them from there.
     constexpr int SX_OFF = FLAG_OFF + 64, SW_OFF = SX_OFF + BM * 4, BI_OFF = SW_OFF + BN * 4, SC_END = BI_OFF + BN * 4;
-    constexpr bool EPI2 = !SELF && ABLK != 50 && ABLK != 60 && (MB % PJ == 0) &&
+    constexpr bool EPI2 = ABLK != 50 && ABLK != 60 && (MB % PJ == 0) &&
                           (((BM * OPITCH + 15) & ~15) + WR_CW * 4 * BM * 4 <= TAILX);   // (the staged tile and the row-maximum slots stay clear of the tail's X_out blocks)
     static_assert(MB % ISSUERS == 0 && (STAGE_BYTES / 1024) % ISSUERS == 0, "pieces must divide evenly over the issuing waves");
-    // (round 6: the tuple-ring form's feed ablations - 1 no weight loads, 2 no X traffic, 3 MFMA only, 6 no k-loop barriers, 32 DMA without fragment
-    // reads, 33 fragment reads without DMA - with pseudo-random stand-ins, and 36: the in-k-step timeline of tools/trace_kstep.py)
-    static_assert(!F6 || (!SELF && (ABLK == 0 || ABLK == 1 || ABLK == 2 || ABLK == 3 || (F6R && (ABLK == 6 || ABLK == 32 || ABLK == 33 || ABLK == 36 || ABLK == 38 || ABLK == 39 || ABL >= 100)))), "the FP6 form exists for the shipped loop (and its feed ablations) only");
-    static_assert(LOOK >= 1 && (LOADS + (ABLK == 76 ? (BN / 16) / (LOADERS ? LOADERS : 1) : 0)) * NEWER < 64, "vmcnt range");
-    static_assert(!SELF || (LOOK == D + 1 && !I4 && ABLK == 0 && (D - 1) * (WNB + LOADS) < 64), "self-loading form: X stage kt+1 and the weights of k-step kt are requested in the same k-step");
+    // (the tuple-ring form's feed ablations - 1 no weight loads, 2 no X traffic, 3 MFMA only - run on pseudo-random stand-ins; 36: the in-k-step
+    // timeline of tools/trace_kstep.py)
+    static_assert(!F6 || ABLK == 0 || ABLK == 1 || ABLK == 2 || ABLK == 3 || ABLK == 36, "the FP6 form exists for the shipped loop (and its feed ablations) only");
+    static_assert(LOOK >= 1 && LOADS * NEWER < 64, "vmcnt range");
     static_assert(!EPI2 || SC_END <= 160 * 1024, "X ring + tail blocks + panel flags + scales must fit the 160 KiB of LDS");
     static_assert(!PAIR || (EPI2 && (Q == 0 || Q == 3)), "the paired gate / up epilogue exists in the panel form of the int8 and the FP6 tuple-ring kernels");
     static_assert(!BF || (!PAIR && ABL == 0 && (Q == 0 || Q == 3)), "bf16 forms: the shipped int8 and FP6 tuple-ring loops, no paired epilogue");
@@ -286,60 +278,6 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
 #endif
     };
     stamp(0);
-#ifdef MIXQ_TUNING
-    // ---- ABL 77, timing probe (NOTEBOOK.md round 6, "the one-launch form"): what would ONE launch for quantise + GEMM cost?  Every workgroup first runs a
-    // stand-in quantise pass over its share of the token rows - the row's fp16 values in (16 bytes per thread and chunk), maximum through DPP + LDS,
-    // scale, eight conversions per chunk, 8 bytes out per chunk with WRITE-THROUGH stores into a scratch image (the GEMM below keeps reading the real q_x:
-    // the launch's results stay correct), drain, ONE agent-scope atomic add per row on the counter of the row's 128-row M tile - then the GEMM as it is,
-    // whose loader waves poll their M tile's counter (bounded: a bug ends in a slow launch, not a hung box) in front of their first activation
-    // stage while the consumer waves are already requesting weights; the last poller of a tile resets its counters.  No outlier handling in the
-    // stand-in (the real pass spends ~0.9 of its 3 us there).
-    if constexpr (ABLK == 77) {
-        if (a.fx) {
-            const int nch = a.fK >> 3;                                             // 16-byte chunks per row
-            if (tid == 0) *reinterpret_cast<volatile uint32_t*>(lds + NSTAGE * STAGE_BYTES - 16) = 0u;      // (the loaders' relay word: LDS is not cleared between launches)
-            // ONE ROW PER WAVE (wave w of workgroup b: row w x workgroups + b): one far round trip for the row, the maximum inside the wave, no LDS, no
-            // workgroup barrier; the first form walked a workgroup's two or three rows one after the other with all six waves (47.7-59 us per forward)
-            const int r = wave * static_cast<int>(gridDim.x) + static_cast<int>(blockIdx.x);
-            if (r < a.M && nch <= 64 * 16) {
-                const uint16_t* xr = a.fx + static_cast<size_t>(r) * a.fK;
-                constexpr int CH = 16;                                             // chunks per lane at most (K <= 8192)
-                u32x4 c[CH];
-#pragma unroll
-                for (int q = 0; q < CH; ++q) { c[q] = u32x4{0, 0, 0, 0}; if (q * 64 + lane < nch) c[q] = *reinterpret_cast<const u32x4*>(xr + (q * 64 + lane) * 8); }
-                uint32_t m = 0;
-#pragma unroll
-                for (int q = 0; q < CH; ++q)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { const uint32_t v = c[q][e] & 0x7fff7fffu; const uint32_t lo = v & 0xffffu, hi = v >> 16; m = m > lo ? m : lo; m = m > hi ? m : hi; }
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) { const uint32_t o = __shfl_xor(m, off); m = m > o ? m : o; }
-                const float amax = h2f(static_cast<uint16_t>(m));
-                const float inv = amax > 0.f ? 127.f / amax : 0.f;
-                const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(a.fq + static_cast<size_t>(r) * a.fK, 0, a.fK, 0x00020000);
-#pragma unroll
-                for (int q = 0; q < CH; ++q) {
-                    const int ch = q * 64 + lane;
-                    if (ch < nch) {
-                        u32x2 o = {0u, 0u};
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const int q0 = static_cast<int>(__builtin_rintf(h2f(static_cast<uint16_t>(c[q][e] & 0xffffu)) * inv));
-                            const int q1 = static_cast<int>(__builtin_rintf(h2f(static_cast<uint16_t>(c[q][e] >> 16)) * inv));
-                            const uint32_t pair = (static_cast<uint32_t>(q0) & 0xffu) | ((static_cast<uint32_t>(q1) & 0xffu) << 8);
-                            if (e < 2) o.x |= pair << (16 * e); else o.y |= pair << (16 * (e - 2));
-                        }
-                        if (!(a.fflags & 1)) { if (a.fflags & 16) __builtin_amdgcn_raw_buffer_store_b64(o, rq, ch * 8, 0, 0); else __builtin_amdgcn_raw_buffer_store_b64(o, rq, ch * 8, 0, 16 /* sc1: write-through */); }
-                        else asm volatile("" :: "v"(o));
-                    }
-                }
-                if (!(a.fflags & 2)) wr_wait_vmcnt<0>();
-                if (lane == 0 && !(a.fflags & 4)) __hip_atomic_fetch_add(a.fcnt + r / BM, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            __syncthreads();                                                      // (the relay word is cleared before a loader can set it)
-        }
-    }
-#endif
     // second set of stamps (tools/trace_gemm.py --panels): the same buffer 16 x 4096 entries further on; `who`: the thread that stamps
     auto stamp2 = [&](int slot, int who) MIXQ_INL {
 #ifdef MIXQ_TUNING
@@ -358,7 +296,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
     // the panel) carry an offset that is always out of range: no address arithmetic and no test per store.
     constexpr int CPR = BNO / 8;                                                 // 16-byte chunks per tile row
     constexpr int CPCH = PROWS * CPR;                                            // ... per panel
-    constexpr int IT_L = SELF ? 1 : (CPCH + LOADERS * 64 - 1) / (LOADERS * 64 > 0 ? LOADERS * 64 : 1);   // per loader thread
+    constexpr int IT_L = (CPCH + LOADERS * 64 - 1) / (LOADERS * 64);                   // per loader thread
     constexpr int IT_A = (CPCH + NT - 1) / NT;                                   // per thread when every wave copies (the last panel)
     auto copy_setup = [&](int t, auto nthr_c, uint32_t* voff, int* loff) MIXQ_INL {
         constexpr int NTHR = decltype(nthr_c)::value, IT = (CPCH + NTHR - 1) / NTHR;
@@ -381,7 +319,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
         for (int it = 0; it < IT; ++it) v[it] = *reinterpret_cast<const u32x4*>(lds + p * PROWS * OPITCH + loff[it]);
         if (ABLK != 7 || a.act == 12345) {
 #pragma unroll
-            for (int it = 0; it < IT; ++it) __builtin_amdgcn_raw_buffer_store_b128(v[it], rs, voff[it], 0, ABLK == 8 ? 0 : (PAIR ? MIXQ_PAIR_ST : (MB <= MIXQ_Y_WT_MB ? 18 : MIXQ_Y_ST)));
+            for (int it = 0; it < IT; ++it) __builtin_amdgcn_raw_buffer_store_b128(v[it], rs, voff[it], 0, PAIR ? MIXQ_PAIR_ST : (MB <= MIXQ_Y_WT_MB ? 18 : MIXQ_Y_ST));
         }
     };
     uint32_t voffA[IT_A];                                                        // this thread's chunks when all NT threads copy a panel
@@ -390,9 +328,8 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
     // =================================================================================================================
     // loader wave(s): X stage kt+LOOK issued, stage kt+1 retired, then the k-step's barrier
     // =================================================================================================================
-    if constexpr (!SELF) {
     if (wave >= CW) {
-        __builtin_amdgcn_s_setprio((FL & 8) ? 0 : 2);
+        __builtin_amdgcn_s_setprio(2);
         const int lw = wave - CW;
         const uint8_t* src[LOADS];
         int dsto[LOADS];
@@ -414,8 +351,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                 // 28-31}, ... (MI355X_MICROARCH.md, LDS), for which the UNswapped rows are conflict-free (bank quads 6 r + g mod 16: evens from one
                 // half of a group, odds from the other) and the swapped ones collide two-way in every group: SQ_LDS_BANK_CONFLICT 1.10 M cycles per
                 // launch = 128 per k-step and CU, every b128 fragment read at half rate (profiles/r06_w4a4_loop.txt)
-                constexpr bool OLDSWZ = (FL & 128) != 0;
-                const int off = within ^ (((within / 96) >= 8 && (OLDSWZ || (within % 96) >= 64)) ? 16 : 0);
+                const int off = within ^ (((within / 96) >= 8 && (within % 96) >= 64) ? 16 : 0);
                 src[i] = a.qx + static_cast<size_t>(rb) * BLK + off;
             } else {
                 int rb = (m0 >> 4) + p; rb = rb < a.xblocks ? rb : a.xblocks - 1;  // blocks past M: loaded, computed, dropped
@@ -429,73 +365,23 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             for (int i = 0; i < LOADS; ++i) src[i] += static_cast<size_t>(kbeg) * xks;
         }
         size_t xoff = 0;                                 // byte offset of the k-step the next stage reads
-        // (ABLK 76, timing probe, results are garbage: what would the loop cost with the WEIGHTS staged through LDS by the loader waves - 1 KiB
-        // LDS-DMA pieces of the tile's weight blocks into one 12 KiB region behind the scales, the consumers reading their fragments from there with
-        // ds_read_b128 instead of issuing vector loads themselves.  A vector load costs the issuing consumer wave ~39 cycles of its k-step, a fragment
-        // read ~13: profiles/r05_ablations_random_operands.txt, r06_w8a8_kstep_timeline.txt)
-        constexpr int WPL = WPROBE ? (BN / 16) / LOADERS : 0;
-        const uint8_t* wsrc[WPL > 0 ? WPL : 1];
-        size_t woffL = 0;
-        if constexpr (WPROBE) {
-#pragma unroll
-            for (int i = 0; i < WPL; ++i) {
-                int rb = (n0 >> 4) + lw + i * LOADERS; rb = rb < a.wblocks ? rb : a.wblocks - 1;
-                wsrc[i] = a.qw + static_cast<size_t>(rb) * 1024 + lane * 16;
-            }
-        }
         auto stage = [&](int slot) MIXQ_INL {
-            if constexpr (ABLK != 2 && ABLK != 3 && ABLK != 33) {
+            if constexpr (ABLK != 2 && ABLK != 3) {
 #pragma unroll
-                for (int i = 0; i < LOADS; ++i) {
-                    wr_glds16(src[i] + xoff, lds + slot * STAGE_BYTES + dsto[i]);
-                    if constexpr (ABLK == 22 || ABLK == 23 || (FL & 2)) __builtin_amdgcn_s_sleep(1);     // probe: the loader's pieces spread over the k-step
-                    if constexpr (ABLK == 24) __builtin_amdgcn_s_sleep(2);
-                }
-                if constexpr (WPROBE) {
-#pragma unroll
-                    for (int i = 0; i < WPL; ++i) wr_glds16(wsrc[i] + woffL, lds + SC_END + (lw + i * LOADERS) * 1024);
-                    woffL += static_cast<size_t>(a.wblocks) * 1024;
-                    if (woffL >= static_cast<size_t>(a.wblocks) * 1024 * nk_all) woffL = 0;
-                }
+                for (int i = 0; i < LOADS; ++i) wr_glds16(src[i] + xoff, lds + slot * STAGE_BYTES + dsto[i]);
             }
             xoff += xks;
         };
-        constexpr int LPS = LOADS + WPL;                 // load instructions per stage and loader wave (the counted waits below)
+        constexpr int LPS = LOADS;                       // load instructions per stage and loader wave (the counted waits below)
         // Deep rings start with a RAMP: all 232 workgroups asking for LOOK stages at once (14 x 8 KiB each at the metric tile) puts
         // 26 MB of requests in front of everybody's first stage.  RP stages are requested up front, then two per k-step until the
         // loader is LOOK stages ahead.  (slot of stage RP + 2 i + 1 was last read LOOK + 2 k-steps earlier: free, as in steady state)
         // (FP6 form at 128-row tiles: 8 stages of 12 KiB - three up front instead of all six: -0.6 .. -1.1 % per launch, same-run A/B of two builds)
-        constexpr int RP = (LOOK > 6 && ABLK != 12) ? 4 : (F6 && LOOK > 3 ? 3 : LOOK);
-#ifdef MIXQ_TUNING
-        if constexpr (ABLK == 77) {
-            if (a.fx && !(a.fflags & 8)) {                // (probe: the loaders wait for their M tile's rows - the consumers are already requesting weights)
-                const unsigned want = static_cast<unsigned>(a.M - m0 < BM ? a.M - m0 : BM);
-                int spins = 0;
-                // ONE lane of ONE loader wave polls, every ~0.5 us (all 64 lanes of 464 waves on four words: 55-59 us per forward - the words' memory channel
-                // serialises the polls and the producers' adds behind them); the other loader wave watches a word in LDS (SC_END: behind the scales)
-                volatile uint32_t* ldsflag = reinterpret_cast<volatile uint32_t*>(lds + NSTAGE * STAGE_BYTES - 16);     // (the ring's last 16 bytes: stage NSTAGE - 1 lands long after)
-                if (lw == 0) {
-                    if (lane == 0) {
-                        while (__hip_atomic_load(a.fcnt + tm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want && ++spins < (1 << 14)) __builtin_amdgcn_s_sleep(16);
-                        *ldsflag = 0x600DF00Du;
-                    }
-                } else if (lane == 0) {
-                    while (*ldsflag != 0x600DF00Du && ++spins < (1 << 18)) __builtin_amdgcn_s_sleep(2);
-                }
-                if (lw == 0 && lane == 0) {
-                    const unsigned seen = __hip_atomic_fetch_add(a.fcnt + a.tiles_m + tm, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (seen == static_cast<unsigned>(a.tiles_n) - 1u) {                // the tile's last poller: everybody has passed
-                        __hip_atomic_store(a.fcnt + a.tiles_m + tm, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(a.fcnt + tm, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-            }
-        }
-#endif
+        constexpr int RP = LOOK > 6 ? 4 : (F6 && LOOK > 3 ? 3 : LOOK);
         int nxt, kt = 0;
         if (RP < LOOK && nk >= 2 * LOOK) {
 #pragma unroll
-            for (int s = 0; s < RP; ++s) { stage(s); if constexpr (ABLK == 26 || ABLK == 27) { if (s == 0) __builtin_amdgcn_s_sleep(8); } }
+            for (int s = 0; s < RP; ++s) stage(s);
             wr_wait_vmcnt<LPS * (RP - 1)>();
             __builtin_amdgcn_s_barrier();                                        // B0: stage 0 landed
             wr_static_for<0, LOOK - RP>([&](auto i_c) MIXQ_INL {
@@ -503,7 +389,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                 stage((RP + 2 * i) % NSTAGE);
                 stage((RP + 2 * i + 1) % NSTAGE);
                 wr_wait_vmcnt<LPS * (RP + i)>();                               // stage i + 1 landed: RP + i younger stages may be in flight
-                if constexpr (ABLK != 6) __builtin_amdgcn_s_barrier();
+                __builtin_amdgcn_s_barrier();
             });
             kt = LOOK - RP;
             nxt = (2 * LOOK - RP) % NSTAGE;
@@ -515,28 +401,6 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             __builtin_amdgcn_s_barrier();                                        // B0: stage 0 landed
             nxt = LOOK % NSTAGE;
         }
-        // TOUCH (probe, ABLK 70 / 71): the weight lines of k-step kt + LOOK are pulled into this XCD's L2 ten k-steps before the consumers
-        // ask for them - one dword per 64-byte sector, this workgroup's share of the panel only (the gm workgroups of an XCD that stream
-        // the same weight panel split its 12 KB per k-step between them), result never read.  Cold weights (a model's layers: every
-        // launch streams 45 MB from HBM) stall the k loop by 100 cycles per k-step (profiles/r04_gemm_trace_warm_cold.txt): long-latency
-        // requests hold the CU's memory queue.  Issued behind the k-step's wait: the hand-counted waits only get stricter by it.
-        constexpr bool TOUCH = ABLK == 70 || ABLK == 71;
-        const uint8_t* tbase = nullptr;
-        int tlanes = 0;
-        if constexpr (TOUCH) {
-            const int nshare = a.gm < a.tiles_m ? a.gm : a.tiles_m;              // workgroups of this XCD sharing the panel (M fastest inside a group)
-            const int sectors = BN;                                              // 64-byte sectors of the panel per k-step (BN x 64 bytes)
-            const int per = (sectors + nshare - 1) / nshare;
-            const int q = tm % nshare;
-            int sec = q * per + lane;
-            const size_t slab = static_cast<size_t>(a.wblocks) * 1024;           // bytes of one k-step of the image
-            size_t off = static_cast<size_t>(n0 >> 4) * 1024 + static_cast<size_t>(sec) * 64;
-            if (off + 64 > slab) off = slab - 64;                                // (the last tile's panel hangs over the image's rows)
-            tbase = a.qw + off;
-            tlanes = (lane < per && sec < sectors && lw == (ABLK == 71 ? 1 : 0)) ? 1 : 0;
-        }
-        size_t toff = static_cast<size_t>(kt + LOOK) * static_cast<size_t>(a.wblocks) * 1024;   // (the k-step whose stage the next iteration requests)
-        int tsink = 0;
         // ABLK 36 (tools/trace_kstep.py): s_memtime stamps inside ONE k-step (k-step nk / 2; the test sits inside the asm statement, so the other
         // k-steps pay a compare and a branch per stamp): the loader's issue / wait / barrier here, the consumer's waits and MFMA groups below
         unsigned long long lst[4] = {0ull, 0ull, 0ull, 0ull};
@@ -548,89 +412,18 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             (void)i; (void)ktv;
 #endif
         };
-#ifdef MIXQ_TUNING
-        // Cross-layer prefetch - built, measured, NOT shipped (tuning library only; profiles/r06_cold_prefetch_ab.txt,
-        // r06_sprefetch_ubench.txt).  A model's layers stream their weights from HBM (the 256 MB memory-side cache holds the last ~5 layers'
-        // images), which costs the metric launch +3 ... 4.6 us.  The idea: this launch's idle loader waves touch one dword per 128-byte line
-        // of the NEXT launch's image so that it sits in the memory-side cache when its GEMM starts.  Two forms:
-        //  (1) through the SCALAR cache - s_load_dword, a path to the L2 that bypasses the L1 and this wave's in-order vmcnt queue; up to PFB
-        //      batches of four lines per k-step while fewer than 12 of the wave's 15 possible requests are in flight (IB_STS.LGKM_CNT), junk
-        //      destination s98 / s99.  The L2 does fetch whole lines that way (FETCH_SIZE of a touch pass = that of a full read) but the
-        //      memory-side cache does not KEEP them: a dependent-load chase over the image takes 0.70 us per load behind such a pass, as on a
-        //      cold image (0.71), against 0.46 behind plain vector loads - the same holds for vector loads with the nt hint.  Forward with
-        //      344 MB of images in rotation: 33.5 -> 34.3 ... 34.8 us; with 172 MB (all resident): 29.6 -> 33.0 us.
-        //  (2) plain vector loads, 64 lines per instruction every few k-steps: the lines are kept (the next launch does run from the cache),
-        //      but every far request holds one of the CU's L1 miss entries for an HBM round trip - the window the k loop's own requests turn
-        //      over in (NOTEBOOK.md round 4) - and the two effects cancel: 33.8 -> 33.5 ... 33.7 us cold, 30.8 -> 31.4 us when all images are
-        //      resident; with the nt hint (not kept, HBM read twice) 33.7 -> 38.0 us.
-        // No path from a CU fills the memory-side cache without paying for it in the CU's own request window; the product library carries none.
-        constexpr int PFB = 4;
-        const uint8_t* pfp = nullptr;
-        int pfn = 0;                                                             // batches of four lines left
-        if constexpr (!KS) {
-            if (a.pf && (a.pf_mode & 1)) {
-                const unsigned per = (a.pf_lines / (static_cast<unsigned>(gridDim.x) * LOADERS)) & ~3u;
-                pfp = a.pf + static_cast<size_t>(blockIdx.x * LOADERS + lw) * per * 128;
-                pfn = static_cast<int>(per >> 2);
-            }
-        }
-        // (mode 2, experiment: ONE vector load of one dword per line - 64 lines per instruction - every PFV k-steps.  It sits in this wave's in-order
-        // vmcnt queue: the stage wait below only gets stricter by it, and passes unhindered as long as the far load returns within NEWER k-steps)
-        int pfv = 0;                                                             // vector instructions left
-        int pfv_every = 1, pfv_cnt = 0;
-        const uint8_t* pfvp = nullptr;
-        int pfsink = 0;
-        if constexpr (!KS) {
-            if (a.pf && (a.pf_mode & 2)) {
-                const unsigned per = (a.pf_lines / (static_cast<unsigned>(gridDim.x) * LOADERS)) & ~63u;      // lines per wave, whole instructions
-                pfvp = a.pf + static_cast<size_t>(blockIdx.x * LOADERS + lw) * per * 128 + static_cast<size_t>(lane) * 128;
-                pfv = static_cast<int>(per >> 6);
-                const int span = nk - LOOK - 6;
-                pfv_every = pfv > 0 && span > pfv ? span / pfv : 1;
-                if (!(a.pf_mode & 1)) pfn = 0;
-            }
-        }
-        auto prefetch_tick = [&]() MIXQ_INL {
-#if defined(__HIP_DEVICE_COMPILE__)
-            if (pfv > 0 && ++pfv_cnt >= pfv_every) {
-                pfv_cnt = 0;
-                if (a.pf_mode & 4) asm volatile("global_load_dword %0, %1, off nt" : "+v"(pfsink) : "v"(pfvp) : "memory"); else asm volatile("global_load_dword %0, %1, off" : "+v"(pfsink) : "v"(pfvp) : "memory");
-                pfvp += 64 * 128;
-                --pfv;
-            }
-#pragma unroll 1
-            for (int b = 0; b < PFB; ++b) {
-                unsigned inflight;
-                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_IB_STS, 8, 4)" : "=s"(inflight));
-                if (inflight > 11u || pfn <= 0) break;
-                const uint8_t* p_ = pfp;
-                asm volatile("s_load_dword s98, %0, 0x0\n\ts_load_dword s98, %0, 0x80\n\ts_load_dword s98, %0, 0x100\n\ts_load_dword s98, %0, 0x180"
-                             :: "s"(p_) : "s98", "s99", "memory");
-                pfp += 512;
-                --pfn;
-            }
-#endif
-        };
-#endif
+        // (Cross-layer prefetch - these idle loader waves touching the NEXT launch's weight image through the scalar cache or with plain vector
+        // loads - was built, measured and removed: no path from a CU fills the memory-side cache without paying for it in the CU's own request
+        // window; profiles/r06_cold_prefetch_ab.txt, r06_sprefetch_ubench.txt.)
         for (; kt + LOOK < nk; ++kt) {
             lstamp(0, kt);
-            if constexpr (FL & 4) __builtin_amdgcn_s_sleep(3);                    // probe: the consumers' first MFMA group behind the barrier runs without the loaders' burst
             stage(nxt);
-#ifdef MIXQ_TUNING
-            if constexpr (!KS) { if ((pfn > 0 || pfv > 0) && kt + LOOK + 4 < nk) prefetch_tick(); }
-#endif
             lstamp(1, kt);
-            if constexpr (ABLK != 5) wr_wait_vmcnt<LPS * NEWER>();              // stage kt+1 landed
+            wr_wait_vmcnt<LPS * NEWER>();              // stage kt+1 landed
             lstamp(2, kt);
-            if constexpr (ABLK != 6) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_barrier();
             lstamp(3, kt);
             nxt = (nxt + 1 == NSTAGE) ? 0 : nxt + 1;
-            if constexpr (TOUCH) {
-                // (the destination stays a LIVE register until the loader's last vmcnt(0): a dead one would be handed to something else while
-                // the load is still in flight, and the returning dword would land in it)
-                if (tlanes) asm volatile("global_load_dword %0, %1, off" : "+v"(tsink) : "v"(tbase + toff) : "memory");
-                toff += static_cast<size_t>(a.wblocks) * 1024;
-            }
         }
         // The fp16 outlier tail's activation operand (X_out rows of this tile) is the same for the four consumer waves: like X it
         // goes through LDS once - fragment-ordered 16 x 32 blocks of the first TQ tail k-steps (64 outlier columns), DMA-ed
@@ -684,7 +477,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
         // ONE tail k-step per drain k-step (its TLOADS pieces take the loader a few hundred cycles of the ~600 it idles per k-step; all at once they
         // made it late for the next barrier), the scales with the first
         bool counted = false;
-        if constexpr (CDRAIN && ABLK != 6 && ABLK != 5) {
+        if constexpr (CDRAIN) {
             if (nk > LOOK) {                              // (the main loop has run: stage kt + 1 .. nk - 1 are the LOOK - 1 stages in flight)
                 counted = true;
                 wr_static_for<0, LOOK - 1>([&](auto d_c) MIXQ_INL {
@@ -711,14 +504,10 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             }
             for (; kt + 1 < nk; ++kt) {
                 wr_wait_vmcnt<0>();
-                if constexpr (ABLK != 6) __builtin_amdgcn_s_barrier();
+                __builtin_amdgcn_s_barrier();
             }
         }
         wr_wait_vmcnt<0>();                                                      // (nk = 1: no drain iteration waited for the tail blocks)
-#ifdef MIXQ_TUNING
-        if constexpr (!KS) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pfsink) :: "s98", "s99", "memory");   // (the prefetch's junk returns: all in before anything else may use the registers)
-#endif
-        if constexpr (TOUCH) asm volatile("" :: "v"(tsink));
 #ifdef MIXQ_TUNING
         if constexpr (TL) {
             asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(lst[0]), "+s"(lst[1]), "+s"(lst[2]), "+s"(lst[3]));
@@ -771,7 +560,6 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             // EPI2: panels 0 .. LP-1 are copied out HERE, each as soon as all four consumer waves have raised its flag, under the consumers'
             // work on the later panels (which are shared by all waves behind the closing barrier).  Outputs that cannot be staged are
             // stored by the consumers themselves.
-            if constexpr (ABLK == 62) __builtin_amdgcn_s_setprio(0);              // probe: the copying loaders below the consumers they share SIMDs with
             stamp2(8, CW * 64);
             if (staged) {
 #pragma unroll
@@ -792,7 +580,6 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             __builtin_amdgcn_s_barrier();
         }
     }
-    }
 
     // =================================================================================================================
     // consumer waves
@@ -801,34 +588,11 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
     const int nw0 = n0 + wave * WN;                                              // first weight row of this wave (wave < CW)
     using acc_t = std::conditional_t<F6, f32x4, i32x4>;                          // (FP6 pipe: fp32 accumulators holding exact integers)
     acc_t acc[MB][WNB];
-    // (tuning probes 78 / 79, garbage results: what would the k loop of the 128 x 256 tile cost on v_mfma_i32_32x32x32_i8 - half the MFMA instructions and half
-    // the operand-register reads per MAC of the 16 x 16 x 64 form, same operand bytes?  78 = sixteen 32 x 32 x 32 MFMAs per k-step into shadow accumulators,
-    // 79 = the shipped thirty-two 16 x 16 x 64 MFMAs into shadow accumulators; both run the epilogue on zeros, so the launches differ by the loop alone)
-    typedef int i32x16_t __attribute__((ext_vector_type(16)));
-    constexpr bool P32 = ABLK == 78, PSH = ABLK == 78 || ABLK == 79;
-    static_assert(!PSH || (MB == 8 && WNB == 4 && Q == 0), "the 32 x 32 x 32 probe is written for the 128 x 256 int8 tile");
-    i32x16_t acc32[P32 ? 4 : 1][P32 ? 2 : 1];
-    i32x4 accs[ABLK == 79 ? MB : 1][ABLK == 79 ? WNB : 1];
-    if constexpr (P32) {
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc32[m][nb][e] = 0;
-    }
-    if constexpr (ABLK == 79) {
-#pragma unroll
-        for (int j = 0; j < MB; ++j)
-#pragma unroll
-            for (int i = 0; i < WNB; ++i) accs[j][i] = i32x4{0, 0, 0, 0};
-    }
     uint16_t sxh[MB];
     u32x2 swp[WNB], bvp[WNB];                                                    // scale_col and bias of this wave's columns, requested with the scales
     int n_out_dev_v = 0;
 
     if (wave < CW) {
-        if constexpr (ABLK == 28 || (FL & 16)) __builtin_amdgcn_s_setprio(3);     // probe: the MFMA waves above the loaders
         if (a.n_out_dev) n_out_dev_v = *a.n_out_dev;
         auto zero_acc = [&]() MIXQ_INL {
 #pragma unroll
@@ -836,7 +600,6 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
 #pragma unroll
                 for (int i = 0; i < WNB; ++i) acc[j][i] = acc_t{0, 0, 0, 0};
         };
-        if constexpr (SELF) zero_acc();                                          // (the others: behind their first operand requests)
 
         // weight stream (round 6): ONE buffer resource over the image, this wave's first block and lane in ONE offset register, the fragment's
         // block as the instruction's immediate offset, the k-step's byte offset as its scalar offset - no address arithmetic per load and two
@@ -877,7 +640,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
         // activation fragment (row lm, k-chunk lq) inside a P16X64 block: conflict-free by the layout's swizzle (common.h);
         // F6: the fragment's 16-byte and 8-byte pieces in the LDS image of an R6X128 block (see the loader)
         const int xoff8 = lm * 96 + 64 + ((lq ^ ((lm >> 3) << 1)) << 3);
-        const int xoff = F6 ? lm * 96 + ((((FL & 128) ? lq ^ (lm >> 3) : lq)) << 4) : lm * 64 + ((lq ^ ((0 - (lm >> 2)) & 3)) << 4);
+        const int xoff = F6 ? lm * 96 + (lq << 4) : lm * 64 + ((lq ^ ((0 - (lm >> 2)) & 3)) << 4);
         // Weight register ring: NSLOT = D + 1 slots.  k-step kt is consumed from slot kt % NSLOT while the loads of k-step kt + D
         // go into slot (kt + D) % NSLOT - the slot the PREVIOUS k-step freed - so they can be issued anywhere inside the step,
         // one behind every few MFMAs, instead of as a burst at its end (a VMEM issue blocks its wave while the address unit is
@@ -885,11 +648,10 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
         constexpr int NSLOT = D + 1;
         i32x4 wq[NSLOT][WNB];
         i32x4 xf[MB];
-        i32x2 wq2[F6 ? NSLOT : 1][F6 ? WNB : 1];                                 // F6: the 8-byte pieces of the 24-byte weight fragments
         // F6: activation fragments as the 6-register operand tuples - a rotating window of XR of a k-step's MB fragments (all MB would
         // not fit next to 6-register weight fragments: 256 registers per wave at 6 waves per CU).  Group j runs on window slot j % XR and
         // requests fragment j + XR behind its last MFMA - of this stage, or of the next one (landed: the k-step's barrier) once j + XR >= MB.
-        constexpr int XR = F6 ? ((ABLK == 38 || (FL & 1)) ? MB : (ABLK == 39 ? 2 : (MB < MIXQ_XR ? MB : MIXQ_XR))) : 1;   // (ABLK 38 / 39, tuning build: window of MB / of 2 tuples)
+        constexpr int XR = F6 ? (MB < MIXQ_XR ? MB : MIXQ_XR) : 1;
         i32x6 xf6[XR];
         static_assert(!F6 || MB % XR == 0, "window slots must be compile-time");
 #pragma unroll
@@ -899,13 +661,16 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                 // the ring's registers are read-write operands of the load statements, so they need a definition in front of the first one:
                 // an EMPTY asm output (no instruction; 15 x 4 v_mov in front of the first weight request otherwise).  Ablation builds that
                 // never load them get defined, opaque values.
-                if constexpr (ABLK == 0 || ABLK == 6 || ABLK == 50 || (ABLK >= 60 && ABLK < 80)) {
+                if constexpr (ABLK == 0 || ABLK == 50 || ABLK == 60) {
                     asm volatile("" : "=v"(wq[d][i]));
-                    if constexpr (F6) asm volatile("" : "=v"(wq2[d][i]));
+                    // (a leftover of the first FP6 form, whose ring held a fragment's 8-byte piece in a register pair of its own: nothing reads the pair,
+                    // but without this empty definition the FP6 kernels come out 12-48 bytes shorter - a different register assignment - and this
+                    // file's code objects are pinned byte for byte, profiles/probe_retirement_code_objects.txt.  To go with the next change that
+                    // re-measures those kernels anyway.)
+                    if constexpr (F6) { i32x2 pair8; asm volatile("" : "=v"(pair8)); }
                 } else {
                     if constexpr (RNDOPS) { const unsigned h = static_cast<unsigned>(lane) * 0x9E3779B1u + static_cast<unsigned>(d * WNB + i + 1) * 0x85EBCA6Bu; wq[d][i] = i32x4{static_cast<int>(h), static_cast<int>(h * 0x27D4EB2Fu), static_cast<int>(h ^ 0x5bd1e995u), static_cast<int>(h * 0x165667B1u)}; }
                     else wq[d][i] = i32x4{lane, lane, lane, lane};
-                    if constexpr (F6) wq2[d][i] = i32x2{lane, lane};
                     asm volatile("" : "+v"(wq[d][i]));
                 }
             }
@@ -937,13 +702,6 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                         for (int i = 0; i < WNB; ++i) { wr6[d][i] = rnd6(1u + d * WNB + i); asm volatile("" : "+v"(wr6[d][i])); }
                 }
 #endif
-            } else if constexpr (F6) {
-#pragma unroll
-                for (int j = 0; j < XR; ++j) xf6[j] = i32x6{lane, 1, lane, 1, 2, 3};
-#pragma unroll
-                for (int d = 0; d < NSLOT; ++d)
-#pragma unroll
-                    for (int i = 0; i < WNB; ++i) asm volatile("" : "+v"(wq2[d][i]));
             }
         }
         // The weight loads are inline asm with hand-counted waits: left to the compiler, the loop header of the unrolled k loop
@@ -959,10 +717,6 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                 i32x4& dst = wq[d][i];
                 const i32x4 rs_ = wrs; const unsigned so_ = woff; const int im_ = wimm(i);   // (named outside the statement: implicit capture does not look into asm operands)
                 const int l16 = wv16(i);
-                if constexpr (WPROBE) {                    // (probe: the fragment comes out of the loaders' LDS copy of the tile's weight blocks)
-                    const unsigned wa = static_cast<unsigned>(reinterpret_cast<size_t>((__attribute__((address_space(3))) uint8_t*)lds)) + SC_END + (wave * WNB) * 1024 + lane * 16;
-                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst) : "v"(wa), "i"(i * 1024) : "memory");
-                } else
                 asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:%4" : "+v"(dst) : "v"(l16), "s"(rs_), "s"(so_), "i"(im_) : "memory");
             }
             else if constexpr (ABLK != 1 && ABLK != 3) {
@@ -970,12 +724,6 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                 i32x4& dst = wq[d][i];                     // (named outside the statement: implicit capture does not look into asm operands)
                 const i32x4 rs_ = wrs; const unsigned so_ = woff; const int im_ = wimm(i);   // (named outside the statement: implicit capture does not look into asm operands)
                 const int l16 = wv16(i);
-                if constexpr (F6) {
-                    i32x2& dst2 = wq2[d][i];
-                    const int l8 = wv8(i);
-                    asm volatile("s_cmp_eq_u32 %6, 0\n\ts_cbranch_scc1 1f\n\tbuffer_load_dwordx4 %0, %2, %4, %5 offen offset:%7\n\tbuffer_load_dwordx2 %1, %3, %4, %5 offen offset:%7\n1:"
-                                 : "+v"(dst), "+v"(dst2) : "v"(l16), "v"(l8), "s"(rs_), "s"(so_), "s"(cs), "i"(im_) : "memory", "scc");
-                } else
                 asm volatile("s_cmp_eq_u32 %4, 0\n\ts_cbranch_scc1 1f\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen offset:%5\n1:"
                              : "+v"(dst) : "v"(l16), "s"(rs_), "s"(so_), "s"(cs), "i"(im_) : "memory", "scc");
             }
@@ -987,12 +735,6 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                 i32x4& dst = wq[d][i];
                 const i32x4 rs_ = wrs; const unsigned so_ = woff; const int im_ = wimm(i);   // (named outside the statement: implicit capture does not look into asm operands)
                 const int l16 = wv16(i);
-                if constexpr (F6) {
-                    i32x2& dst2 = wq2[d][i];
-                    const int l8 = wv8(i);
-                    asm volatile("buffer_load_dwordx4 %0, %2, %4, %5 offen offset:%6\n\tbuffer_load_dwordx2 %1, %3, %4, %5 offen offset:%6"
-                                 : "+v"(dst), "+v"(dst2) : "v"(l16), "v"(l8), "s"(rs_), "s"(so_), "i"(im_) : "memory");
-                } else
                 asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:%4" : "+v"(dst) : "v"(l16), "s"(rs_), "s"(so_), "i"(im_) : "memory");
             }
         };
@@ -1014,10 +756,6 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                 if constexpr (WNB == 2) asm volatile("s_waitcnt vmcnt(%2)" : "+v"(wq[d][0]), "+v"(wq[d][1]) : "i"(CNT));
                 if constexpr (WNB == 3) asm volatile("s_waitcnt vmcnt(%3)" : "+v"(wq[d][0]), "+v"(wq[d][1]), "+v"(wq[d][2]) : "i"(CNT));
                 if constexpr (WNB == 4) asm volatile("s_waitcnt vmcnt(%4)" : "+v"(wq[d][0]), "+v"(wq[d][1]), "+v"(wq[d][2]), "+v"(wq[d][3]) : "i"(CNT));
-                if constexpr (F6) {                        // (volatile statements keep their order: the 8-byte pieces are "defined" behind the wait as well)
-#pragma unroll
-                    for (int i = 0; i < WNB; ++i) asm volatile("" : "+v"(wq2[d][i]));
-                }
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
@@ -1045,10 +783,6 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                 if constexpr (WNB == 2) asm volatile(MIXQ_WR_WAITS : "+v"(wq[d][0]), "+v"(wq[d][1]) : MIXQ_WR_WAIT_IN : "scc");
                 if constexpr (WNB == 3) asm volatile(MIXQ_WR_WAITS : "+v"(wq[d][0]), "+v"(wq[d][1]), "+v"(wq[d][2]) : MIXQ_WR_WAIT_IN : "scc");
                 if constexpr (WNB == 4) asm volatile(MIXQ_WR_WAITS : "+v"(wq[d][0]), "+v"(wq[d][1]), "+v"(wq[d][2]), "+v"(wq[d][3]) : MIXQ_WR_WAIT_IN : "scc");
-                if constexpr (F6) {
-#pragma unroll
-                    for (int i = 0; i < WNB; ++i) asm volatile("" : "+v"(wq2[d][i]));
-                }
 #undef MIXQ_WR_WAITS
 #undef MIXQ_WR_WAIT_IN
 #undef MIXQ_WR_W1
@@ -1066,7 +800,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
         const unsigned xbase32 = static_cast<unsigned>(reinterpret_cast<size_t>((__attribute__((address_space(3))) uint8_t*)lds)) + static_cast<unsigned>(xoff);
         const unsigned xbase32_8 = static_cast<unsigned>(reinterpret_cast<size_t>((__attribute__((address_space(3))) uint8_t*)lds)) + static_cast<unsigned>(xoff8);
         auto xread = [&](int slot, int j) MIXQ_INL {
-            if constexpr (F6 && (ABLK == 2 || ABLK == 3 || ABLK == 32)) {
+            if constexpr (F6 && (ABLK == 2 || ABLK == 3)) {
                 // (ablation: no LDS reads)
             } else if constexpr (F6) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1087,10 +821,8 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
         // in front of EVERY group cost the int8 loop 5 % of the launch - the consumer waves are bound by what they issue between their MFMAs
         // (profiles/r06_xwait_bisect.txt) - and one drain per k-step costs the int8 loop nothing measurable.  The FP6 forms' window of XR tuples
         // needs a wait every XR groups at least; theirs is counted, so the youngest read it waits for is XR - XWG groups old.
-        constexpr int XWG_SEL = (FL >> 8) & 3;                                    // (tuning build: 1, 2, 3 -> a wait every 1, 2, 4 groups)
-        constexpr int XWG_DEF = F6 ? (XR < 2 ? XR : 2) : MB;
-        constexpr int XWG0 = ABLK == 73 ? 4 : (ABLK == 74 ? 2 : (ABLK == 75 ? 1 : (XWG_SEL == 1 ? 1 : (XWG_SEL == 2 ? 2 : (XWG_SEL == 3 ? 4 : XWG_DEF)))));
-        constexpr int XWG = XWG0 > (F6 ? XR : MB) ? (F6 ? XR : MB) : XWG0;
+        constexpr int XWG = F6 ? (XR < 2 ? XR : 2) : MB;
+        static_assert(F6 ? XWG <= 2 : (XWG == 1 || XWG == 2 || XWG == 4 || XWG == 8), "xwait / xwait_rt have a statement for these");
         static_assert((F6 ? XR : MB) % XWG == 0, "a wait serves whole groups of the fragment window");
         // DS operations issued behind the read that filled group jt's fragment and in front of group j0 <= jt, in a k-step that re-reads from the
         // next stage (REFILL) or not (the tile's last k-step).  int8 forms: fragment j is re-read behind group j (one operation).  FP6 forms: group
@@ -1102,24 +834,19 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
         };
         // the fragments of groups j .. j + XWG - 1 have landed (a statement in front of group j when j is a multiple of XWG; nothing otherwise)
         auto xwait = [&](int j, bool refill) MIXQ_INL {
-            if constexpr (F6 && (ABLK == 2 || ABLK == 3 || ABLK == 32)) { (void)j; (void)refill; }
+            if constexpr (F6 && (ABLK == 2 || ABLK == 3)) { (void)j; (void)refill; }
             else if (j % XWG == 0) {
                 const int jt = j + XWG - 1;
                 if constexpr (F6) {
 #if defined(__HIP_DEVICE_COMPILE__)
                     if constexpr (XWG == 1) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xf6[j % XR]) : "i"(xyounger(j, jt, refill)));
                     if constexpr (XWG == 2) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(xf6[j % XR]), "+v"(xf6[(j + 1) % XR]) : "i"(xyounger(j, jt, refill)));
-                    if constexpr (XWG == 4) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(xf6[j % XR]), "+v"(xf6[(j + 1) % XR]), "+v"(xf6[(j + 2) % XR]), "+v"(xf6[(j + 3) % XR]) : "i"(xyounger(j, jt, refill)));
 #endif
                 } else if constexpr (ABLK != 2 && ABLK != 3) {
                     if constexpr (XWG == 1) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(xf[j]) : "i"(xyounger(j, jt, refill)));
                     if constexpr (XWG == 2) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(xf[j]), "+v"(xf[j + 1]) : "i"(xyounger(j, jt, refill)));
                     if constexpr (XWG == 4) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(xf[j]), "+v"(xf[j + 1]), "+v"(xf[j + 2]), "+v"(xf[j + 3]) : "i"(xyounger(j, jt, refill)));
                     if constexpr (XWG == 8) asm volatile("s_waitcnt lgkmcnt(%8)" : "+v"(xf[j]), "+v"(xf[j + 1]), "+v"(xf[j + 2]), "+v"(xf[j + 3]), "+v"(xf[j + 4]), "+v"(xf[j + 5]), "+v"(xf[j + 6]), "+v"(xf[j + 7]) : "i"(xyounger(j, jt, refill)));
-                    if constexpr (XWG == 16) {
-                        asm volatile("s_waitcnt lgkmcnt(%8)" : "+v"(xf[j]), "+v"(xf[j + 1]), "+v"(xf[j + 2]), "+v"(xf[j + 3]), "+v"(xf[j + 4]), "+v"(xf[j + 5]), "+v"(xf[j + 6]), "+v"(xf[j + 7]) : "i"(xyounger(j, jt, refill)));
-                        asm volatile("" : "+v"(xf[j + 8]), "+v"(xf[j + 9]), "+v"(xf[j + 10]), "+v"(xf[j + 11]), "+v"(xf[j + 12]), "+v"(xf[j + 13]), "+v"(xf[j + 14]), "+v"(xf[j + 15]));
-                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -1130,24 +857,19 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             const int rf = __builtin_amdgcn_readfirstlane(refill ? 1 : 0);
 #define MIXQ_XWAIT_RT "s_cmp_eq_u32 %[rf], 0\n\ts_cbranch_scc1 1f\n\ts_waitcnt lgkmcnt(%[a])\n\ts_branch 2f\n1:\n\ts_waitcnt lgkmcnt(%[b])\n2:"
 #define MIXQ_XWAIT_IN [rf] "s"(rf), [a] "i"(xyounger(j, jt, true)), [b] "i"(xyounger(j, jt, false))
-            if constexpr (F6 && (ABLK == 2 || ABLK == 3 || ABLK == 32)) { (void)j; (void)rf; }
+            if constexpr (F6 && (ABLK == 2 || ABLK == 3)) { (void)j; (void)rf; }
             else if (j % XWG == 0) {
                 const int jt = j + XWG - 1;
                 if constexpr (F6) {
 #if defined(__HIP_DEVICE_COMPILE__)
                     if constexpr (XWG == 1) asm volatile(MIXQ_XWAIT_RT : "+v"(xf6[j % XR]) : MIXQ_XWAIT_IN : "scc");
                     if constexpr (XWG == 2) asm volatile(MIXQ_XWAIT_RT : "+v"(xf6[j % XR]), "+v"(xf6[(j + 1) % XR]) : MIXQ_XWAIT_IN : "scc");
-                    if constexpr (XWG == 4) asm volatile(MIXQ_XWAIT_RT : "+v"(xf6[j % XR]), "+v"(xf6[(j + 1) % XR]), "+v"(xf6[(j + 2) % XR]), "+v"(xf6[(j + 3) % XR]) : MIXQ_XWAIT_IN : "scc");
 #endif
                 } else if constexpr (ABLK != 2 && ABLK != 3) {
                     if constexpr (XWG == 1) asm volatile(MIXQ_XWAIT_RT : "+v"(xf[j]) : MIXQ_XWAIT_IN : "scc");
                     if constexpr (XWG == 2) asm volatile(MIXQ_XWAIT_RT : "+v"(xf[j]), "+v"(xf[j + 1]) : MIXQ_XWAIT_IN : "scc");
                     if constexpr (XWG == 4) asm volatile(MIXQ_XWAIT_RT : "+v"(xf[j]), "+v"(xf[j + 1]), "+v"(xf[j + 2]), "+v"(xf[j + 3]) : MIXQ_XWAIT_IN : "scc");
                     if constexpr (XWG == 8) asm volatile(MIXQ_XWAIT_RT : "+v"(xf[j]), "+v"(xf[j + 1]), "+v"(xf[j + 2]), "+v"(xf[j + 3]), "+v"(xf[j + 4]), "+v"(xf[j + 5]), "+v"(xf[j + 6]), "+v"(xf[j + 7]) : MIXQ_XWAIT_IN : "scc");
-                    if constexpr (XWG == 16) {
-                        asm volatile(MIXQ_XWAIT_RT : "+v"(xf[j]), "+v"(xf[j + 1]), "+v"(xf[j + 2]), "+v"(xf[j + 3]), "+v"(xf[j + 4]), "+v"(xf[j + 5]), "+v"(xf[j + 6]), "+v"(xf[j + 7]) : MIXQ_XWAIT_IN : "scc");
-                        asm volatile("" : "+v"(xf[j + 8]), "+v"(xf[j + 9]), "+v"(xf[j + 10]), "+v"(xf[j + 11]), "+v"(xf[j + 12]), "+v"(xf[j + 13]), "+v"(xf[j + 14]), "+v"(xf[j + 15]));
-                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -1195,9 +917,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             auto loads_behind = [&](int j) MIXQ_INL {                                     // j: compile-time after unrolling
 #pragma unroll
                 for (int i = 0; i < WNB; ++i) {
-                    int pos = (WNB >= MB) ? (i % MB) : ((2 * i + 1) * MB) / (2 * WNB);      // spread evenly over the MB groups
-                    if constexpr (ABLK == 20 || ABLK == 23) pos = MB - WNB + i;            // probe: behind the last groups (away from the loaders' burst after the barrier)
-                    if constexpr (ABLK == 21) pos = (i * MB) / WNB;                        // probe: 0, 2, 5: earlier
+                    const int pos = (WNB >= MB) ? (i % MB) : ((2 * i + 1) * MB) / (2 * WNB);   // spread evenly over the MB groups
                     if (pos == j) { if constexpr (FULL) wload1_always(LC{}, i); else wload1(LC{}, i, issue); }
                 }
             };
@@ -1225,108 +945,26 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                     if constexpr (TL) { if (j < 8) kstamp(3 + j); __builtin_amdgcn_sched_barrier(0); }
                 }
 #undef MIXQ_F6_MMA
-            } else if constexpr (F6) {
-                // Same order as the int8 loop: weight load behind the group's first MFMA, the fragment's re-read behind its last.
-                // The MFMA is inline asm: the compiler's form of the scaled MFMA is not tied (vdst != srcC, accumulators rotating through
-                // VGPRs), which runs at 32 cycles instead of 19.5 (tools/ubench_fp6.hip) and doubles the accumulator footprint.  In asm
-                // the accumulators stay in place in the AGPR half.  The hazard recogniser does not look into asm, so: the weight
-                // tuples are assembled (v_mov) and pinned BEFORE a scheduling barrier and two wait states; activation tuples come
-                // straight from LDS reads (waited for by the compiler: the asm names them as inputs); consecutive MFMAs never share
-                // an accumulator (24 MFMAs lie between two uses of one).  Accumulators are VGPRs ("+v", in place): with an AGPR class in
-                // play the allocator splits the 256 registers of a wave 128 / 128, and 128 VGPRs do not hold the rings.
-                i32x6 w6[WNB];
-#pragma unroll
-                for (int i = 0; i < WNB; ++i) {
-                    w6[i] = i32x6{wq[C][i][0], wq[C][i][1], wq[C][i][2], wq[C][i][3], wq2[C][i][0], wq2[C][i][1]};
-#if defined(__HIP_DEVICE_COMPILE__)                  // (the host pass parses kernel bodies too and knows no 192-bit "v" operand)
-                    asm volatile("" : "+v"(w6[i]));
-#endif
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                asm volatile("s_nop 1" ::: "memory");
-                const int unit = 0x7f7f7f7f;                                       // E8M0 block scales of 2^0
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MIXQ_F6_MMA(ACC, W, X) asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0] cbsz:3 blgp:3" \
-                                            : "+v"(ACC) : "v"(W), "v"(X), "v"(unit))
-#else
-#define MIXQ_F6_MMA(ACC, W, X) (void)unit
-#endif
-#pragma unroll
-                for (int j = 0; j < MB; ++j) {
-                    if constexpr (FULL) xwait(j, true); else xwait_rt(j, refill);
-                    MIXQ_F6_MMA(acc[j][0], w6[0], xf6[j % XR]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    loads_behind(j);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int i = 1; i < WNB; ++i) MIXQ_F6_MMA(acc[j][i], w6[i], xf6[j % XR]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (j + XR < MB) xread(rslot == 0 ? NSTAGE - 1 : rslot - 1, j + XR);   // (this stage: the slot before stage kt+1's)
-                    else if (refill) xread(rslot, j + XR - MB);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#undef MIXQ_F6_MMA
             } else if constexpr (!I4) {
 #pragma unroll
                 for (int j = 0; j < MB; ++j) {
                     if constexpr (FULL) xwait(j, true); else xwait_rt(j, refill);
-                    constexpr bool NEW_ORDER = ABLK != 31;                        // (31, tuning build: round 2's order)
-                    if constexpr (P32) {
-                        // group g: k-half g >> 2 of row block g & 3 (a 32 x 32 accumulator is touched again four groups = eight MFMAs later)
-                        const int kh = j >> 2, mb32 = j & 3, f = mb32 * 2 + kh;
-#if defined(__HIP_DEVICE_COMPILE__)                  // (with this builtin in sight the HOST pass drops the kernel's stub without a diagnostic)
-                        acc32[mb32][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(wq[C][kh], xf[f], acc32[mb32][0], 0, 0, 0);
-#endif
-                        __builtin_amdgcn_sched_barrier(0);
-                        loads_behind(j);
-                        __builtin_amdgcn_sched_barrier(0);
-#if defined(__HIP_DEVICE_COMPILE__)
-                        acc32[mb32][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(wq[C][2 + kh], xf[f], acc32[mb32][1], 0, 0, 0);
-#endif
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (refill) xread(rslot, f);
-                        __builtin_amdgcn_sched_barrier(0);
-                        continue;
-                    }
-                    if constexpr (ABLK == 79) {
-                        accs[j][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wq[C][0], xf[j], accs[j][0], 0, 0, 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                        loads_behind(j);
-                        __builtin_amdgcn_sched_barrier(0);
+                    // At most ONE memory instruction per MFMA gap: a wave issues in order and a 16-cycle MFMA leaves ~12 cycles in
+                    // which one fragment read or one weight load can be issued for free.  The weight load goes behind the group's
+                    // FIRST MFMA, the fragment's re-read behind its last use (round 2 put both behind the last).  Measured: -1.6 %
+                    // against the old order compiled into the same (tuning) library, -1.8 % / -1.5 % at N = 11008 / 12288 between
+                    // two product builds loaded side by side (profiles/r03_gemm_ab_issue_timing.txt, r03_ab_order_builds.txt).
+                    acc[j][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wq[C][0], xf[j], acc[j][0], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    loads_behind(j);
+                    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                        for (int i = 1; i < WNB; ++i)
-                            accs[j][i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wq[C][i], xf[j], accs[j][i], 0, 0, 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (refill) xread(rslot, j);
-                        __builtin_amdgcn_sched_barrier(0);
-                        continue;
-                    }
-                    if constexpr (NEW_ORDER) {
-                        // At most ONE memory instruction per MFMA gap: a wave issues in order and a 16-cycle MFMA leaves ~12 cycles in
-                        // which one fragment read or one weight load can be issued for free.  The weight load goes behind the group's
-                        // FIRST MFMA, the fragment's re-read behind its last use (round 2 put both behind the last).  Measured: -1.6 %
-                        // against the old order compiled into the same (tuning) library, -1.8 % / -1.5 % at N = 11008 / 12288 between
-                        // two product builds loaded side by side (profiles/r03_gemm_ab_issue_timing.txt, r03_ab_order_builds.txt).
-                        acc[j][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wq[C][0], xf[j], acc[j][0], 0, 0, 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                        loads_behind(j);
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int i = 1; i < WNB; ++i)
-                            acc[j][i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wq[C][i], xf[j], acc[j][i], 0, 0, 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (refill) xread(rslot, j);
-                        __builtin_amdgcn_sched_barrier(0);
-                        if constexpr (TL) { if (j < 8) kstamp(3 + j); __builtin_amdgcn_sched_barrier(0); }
-                        continue;
-                    }
-#pragma unroll
-                    for (int i = 0; i < WNB; ++i)
+                    for (int i = 1; i < WNB; ++i)
                         acc[j][i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wq[C][i], xf[j], acc[j][i], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                     if (refill) xread(rslot, j);
-                    loads_behind(j);
                     __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (TL) { if (j < 8) kstamp(3 + j); __builtin_amdgcn_sched_barrier(0); }
                 }
             } else {
                 // nibbles -> int8 values 16 q: even columns (low nibbles) and odd columns (high nibbles) form two fragments,
@@ -1350,7 +988,6 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
         };
 
         // the epilogue's scales first: the oldest loads of this wave, so they never sit between the hand-counted weight loads
-        // (the fat prefill form requests them after its k loop instead: 24 registers held across the loop would be spilled there)
         auto load_scales = [&]() MIXQ_INL {
 #pragma unroll
             for (int j = 0; j < MB; ++j) {
@@ -1365,93 +1002,11 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                 if constexpr (PREBIAS) bvp[i] = a.bias ? *reinterpret_cast<const u32x2_u*>(a.bias + (n < a.N ? n : a.N - 4)) : u32x2{0u, 0u};
             }
         };
-        if constexpr (SELF) {
-            // ---- self-loading k loop (prefill form) -------------------------------------------------------------------------
-            // Every k-step, in this program order: MB MFMA groups; behind group i*MB/LOADS this wave's piece i of X stage kt+LOOK
-            // (LDS-DMA), behind group ((2i+1) MB)/(2 WNB) weight load i of k-step kt+D; fragment j re-read from stage kt+1 behind its
-            // last MFMA.  LOOK = D + 1: stage kt+1 and the weights of k-step kt were requested in the SAME k-step kt-D, pieces first,
-            // so ONE counted wait - at most (D-1)(WNB+LOADS) younger requests in flight - retires both (vmcnt retires in order).
-            // Requests past the end of K wrap around to the first k-steps (valid addresses, L2-hot, never consumed): every k-step is
-            // the same straight-line code, nothing conditional sits between the hand-counted loads.
-            const uint8_t* xsrc[LOADS];
-            int xdst[LOADS];
-#pragma unroll
-            for (int i = 0; i < LOADS; ++i) {
-                const int p = wave + i * CW;
-                int rb = (m0 >> 4) + p; rb = rb < a.xblocks ? rb : a.xblocks - 1;
-                xsrc[i] = a.qx + static_cast<size_t>(rb) * 1024 + lane * 16;
-                xdst[i] = p * 1024;
-            }
-            const size_t xks = static_cast<size_t>(a.xblocks) * 1024;
-            int xkq = 0;
-            size_t xoff_g = 0;
-            auto xpiece = [&](int slot, int i) MIXQ_INL { wr_glds16(xsrc[i] + xoff_g, lds + slot * STAGE_BYTES + xdst[i]); };
-            auto xadvance = [&]() MIXQ_INL { xoff_g += xks; if (++xkq == nk) { xkq = 0; xoff_g = 0; } };
-            constexpr int INFLIGHT = (D - 1) * (WNB + LOADS);
-            // prologue = the k-steps -D .. -1 of the steady state, preceded by stage 0
-#pragma unroll
-            for (int i = 0; i < LOADS; ++i) xpiece(0, i);
-            xadvance();
-            wr_static_for<0, D>([&](auto d_c) MIXQ_INL {
-                constexpr int d = decltype(d_c)::value;
-#pragma unroll
-                for (int i = 0; i < LOADS; ++i) xpiece((d + 1) % NSTAGE, i);
-                xadvance();
-#pragma unroll
-                for (int i = 0; i < WNB; ++i) wload1_always(d_c, i);
-                wadvance(1);
-            });
-            wr_wait_vmcnt<INFLIGHT>();                                           // own pieces of stages 0 and 1, weights of k-step 0
-            __builtin_amdgcn_s_barrier();                                        // B0: everybody's pieces of stage 0 (and 1) landed
-            stamp(1);
-#pragma unroll
-            for (int j = 0; j < MB; ++j) xread(0, j);
-            int kt = 0, slot1 = 1 % NSTAGE, nxt = LOOK % NSTAGE;                 // ring slots of stage kt+1 and stage kt+LOOK
-            auto one = [&](auto c_c) MIXQ_INL {
-                constexpr int C = decltype(c_c)::value, L = (C + D) % NSLOT;
-                using LC = std::integral_constant<int, L>;
-                wwait(c_c, std::integral_constant<int, INFLIGHT>{});             // weights of k-step kt and own pieces of stage kt+1 landed
-                __builtin_amdgcn_s_barrier();                                    // everybody's: stage kt+1 readable, stage kt-2's slot free
-#pragma unroll
-                for (int j = 0; j < MB; ++j) {
-                    xwait(j, true);                                               // (this form re-reads on every k-step: the wrapped-around stages)
-#pragma unroll
-                    for (int i = 0; i < WNB; ++i)
-                        acc[j][i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wq[C][i], xf[j], acc[j][i], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    xread(slot1, j);
-#pragma unroll
-                    for (int i = 0; i < LOADS; ++i)
-                        if ((i * MB) / LOADS == j) xpiece(nxt, i);
-#pragma unroll
-                    for (int i = 0; i < WNB; ++i)
-                        if (((2 * i + 1) * MB) / (2 * WNB) == j) wload1_always(LC{}, i);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                wadvance(1);
-                xadvance();
-                slot1 = (NSTAGE & (NSTAGE - 1)) == 0 ? ((slot1 + 1) & (NSTAGE - 1)) : ((slot1 + 1 == NSTAGE) ? 0 : slot1 + 1);
-                nxt = (nxt + 1 == NSTAGE) ? 0 : nxt + 1;
-                ++kt;
-            };
-            while (kt + NSLOT <= nk) wr_static_for<0, NSLOT>([&](auto c_c) MIXQ_INL { one(c_c); });
-            {
-                const int k0 = kt;                                               // (a group is entered at ring slot 0)
-                wr_static_for<0, NSLOT>([&](auto c_c) MIXQ_INL { if (k0 + decltype(c_c)::value < nk) one(c_c); });
-            }
-            wr_wait_vmcnt<0>();                                                  // the wrapped-around requests of the last k-steps: nothing may
-            xdrain();                                                            // land in a register the epilogue re-uses
-            load_scales();
-            stamp(2);
-        } else {
         // ---- prologue ------------------------------------------------------------------------------------------------
         auto prologue_w = [&](auto d_c) MIXQ_INL {
 #pragma unroll
             for (int i = 0; i < WNB; ++i) wload1(d_c, i, decltype(d_c)::value < nk ? 1 : 0);
             wadvance(decltype(d_c)::value < nk ? 1 : 0);
-            // probes: hold the requests of k-steps 1.. back so every CU's first k-step is served first
-            if constexpr (ABLK == 25 || ABLK == 26) { if (decltype(d_c)::value == 0) __builtin_amdgcn_s_sleep(8); }
-            if constexpr (ABLK == 27) { if (decltype(d_c)::value == 0) __builtin_amdgcn_s_sleep(16); }
         };
         // Request order: the weights of k-step 0 FIRST - they and the loaders' first stage are what the first MFMA waits for - then the
         // epilogue's scales (round 3 asked for those before anything else: ~30 address instructions and 14 requests in front of the first
@@ -1478,15 +1033,15 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             if constexpr (FULL) {
                 kcur = kt;
                 kstamp(0);
-                if constexpr (ABLK != 4) wwait(c_c, std::integral_constant<int, WL * (D - 1)>{});    // the D-1 younger k-steps stay in flight
+                wwait(c_c, std::integral_constant<int, WL * (D - 1)>{});    // the D-1 younger k-steps stay in flight
                 kstamp(1);
-                if constexpr (ABLK != 6) __builtin_amdgcn_s_barrier();            // stage kt+1 landed; stage kt-2's slot is free
+                __builtin_amdgcn_s_barrier();            // stage kt+1 landed; stage kt-2's slot is free
                 kstamp(2);
                 step(c_c, full_c, true, 1, slot1);
             } else {
                 wwait_rt(c_c, nk - 1 - kt);
                 const bool more = kt + 1 < nk;
-                if (more && ABLK != 6) __builtin_amdgcn_s_barrier();
+                if (more) __builtin_amdgcn_s_barrier();
                 step(c_c, full_c, more, kt + D < nk ? 1 : 0, slot1);
             }
             slot1 = (NSTAGE & (NSTAGE - 1)) == 0 ? ((slot1 + 1) & (NSTAGE - 1)) : ((slot1 + 1 == NSTAGE) ? 0 : slot1 + 1);
@@ -1515,18 +1070,6 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             }
         }
 #endif
-        if constexpr (P32) {
-#pragma unroll
-#if defined(__HIP_DEVICE_COMPILE__)                  // (512-bit "v" operands: device pass only)
-            for (int m = 0; m < 4; ++m) asm volatile("" :: "v"(acc32[m][0]), "v"(acc32[m][1]));
-#else
-            for (int m = 0; m < 4; ++m) (void)acc32[m][0];
-#endif
-        }
-        if constexpr (ABLK == 79) {
-#pragma unroll
-            for (int j = 0; j < MB; ++j) asm volatile("" :: "v"(accs[j][0]), "v"(accs[j][1]), "v"(accs[j][2]), "v"(accs[j][3]));
-        }
         if constexpr (KS) {
             // ---- pairwise split-K hand-off (see KS above): slot = [wave][MB x WNB fragments][64 lanes x 16 bytes], register order ------
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.ks_slots + static_cast<size_t>(tile) * (BM * BN * 4), 0, BM * BN * 4, 0x00020000);
@@ -1558,7 +1101,6 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             }
         }
         stamp(2);
-        }
     }
 
     // =================================================================================================================
@@ -1662,8 +1204,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                 const int j = pn * PJ + b / WNB, i = b % WNB;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    if constexpr (ABLK == 66) fa[j][i][r] = static_cast<float>(acc[j][i][r]);   // probe: no scaling
-                    else fa[j][i][r] = static_cast<float>(acc[j][i][r]) * sxv[j] * swv[i][r];
+                    fa[j][i][r] = static_cast<float>(acc[j][i][r]) * sxv[j] * swv[i][r];
                 }
             };
             // optional terms, fp16, staged or stored: the 16-channel block column i of panel pn (PJ blocks) - the first form's finish_tile, cut
@@ -1720,8 +1261,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                         const us2 mx = __builtin_elementwise_max(__builtin_bit_cast(us2, o.x & keep_lo), __builtin_bit_cast(us2, o.y & keep_hi));
                         rmax[j] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(us2, rmax[j]), mx));
                     }
-                    if constexpr (ABLK == 65) { asm volatile("" :: "v"(o)); }      // probe: converted, never staged
-                    else if constexpr (ST) *reinterpret_cast<u32x2*>(lds + (j * 16 + lm) * OPITCH + nloc * 2) = o;
+                    if constexpr (ST) *reinterpret_cast<u32x2*>(lds + (j * 16 + lm) * OPITCH + nloc * 2) = o;
                     else if (m < a.M && n < a.N) *reinterpret_cast<u32x2_u*>(a.y + static_cast<size_t>(m) * a.ldy + n) = o;
                 }
             };
@@ -1777,7 +1317,6 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                     xo2[kk][jj] = *reinterpret_cast<const u32x4*>(lds + TAILX + (kk * MB + pn * PJ + jj) * 1024 + lane * 16);
             };
             auto tail_mma = [&](int j, int i, u32x4 w, u32x4 x) MIXQ_INL {
-                if constexpr (ABLK == 64) return;                                 // probe: the epilogue without its tail MFMAs (results are garbage)
                 fa[j][i] = wr_tail_mfma<BF>(w, x, fa[j][i]);
             };
             // more than 32 TQ outlier columns (rare: the search stops adding beyond 128, linear.py:224): the remaining k-steps with both
@@ -1882,8 +1421,8 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             stamp(3);
         } else {
         // fp16 outlier tail operands: 16 x 32 fragments, lane = row lm, columns kk*32 + lq*8 .. +8.  TD register sets: with two,
-        // the operands of tail k-step kk+1 are in flight behind the MFMAs of kk; the fattest tiles only have room for one.
-        constexpr int TD = (SELF || MB * WNB * 4 + 2 * (MB + WNB) * 4 + 40 > 256) ? 1 : 2;
+        // the operands of tail k-step kk+1 are in flight behind the MFMAs of kk; tiles without the registers for two get one.
+        constexpr int TD = (MB * WNB * 4 + 2 * (MB + WNB) * 4 + 40 > 256) ? 1 : 2;
         u32x4 xoq[TD][MB], woq[TD][WNB];
         auto tail_load_w = [&](int P, int kk) MIXQ_INL {            // P: constant after unrolling
             const int kb = kk * 32 + lq * 8;
@@ -1955,11 +1494,9 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
         auto tail_mfma1 = [&](int P, int j, int i) MIXQ_INL {
             fa[j][i] = wr_tail_mfma<BF>(woq[P][i], xoq[P][j], fa[j][i]);
         };
-        // PANELS: the fat prefill tile (SELF) holds 256 accumulator registers per lane; dequantised all at once they would need a
-        // second 256 - in VGPRs, since the VALU cannot write AGPRs - next to the tail operands (165 spilled registers, and wrong
-        // results under load).  So its epilogue runs one 16-channel column of blocks (PW = 1 of the WNB) at a time: read from the
-        // accumulator file, dequantise, tail, optional terms, fp16, staged - then the next.  Every other tiling is ONE panel.
-        constexpr int PW = SELF ? 1 : WNB, NP = WNB / PW;
+        // ONE panel: all WNB block columns of the wave at once (the round-3 prefill experiment with 256 accumulator registers per lane ran its
+        // epilogue one column, PW = 1, at a time)
+        constexpr int PW = WNB, NP = WNB / PW;
         auto tail_mma = [&](int P, int kk, auto p_c) MIXQ_INL {
             constexpr int p = decltype(p_c)::value;
             tail_mask(P, kk);                                                    // (idempotent: a set shared by several panels is masked again)
@@ -2105,7 +1642,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
         if (m0 + tid < a.M) atomicMax(a.row_amax + m0 + tid, v);
     }
     if constexpr (EPI2) {
-        if (staged) {                                                 // (ABLK 61, a probe: LP = 0 - everything here, as the first form)
+        if (staged) {                                                 
 #pragma unroll
             for (int p = LP; p < NPAN; ++p) copy_panel(p, std::integral_constant<int, NT>{}, voffA, loffA);   // (the earlier panels left under the arithmetic)
         }
@@ -2127,8 +1664,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             const int m = m0 + r, n = n0 + c * 8;
             // streaming (nt) store: Y is written once and not re-read by this kernel
             if (q < BM * CPR && m < a.M && n < a.N && (ABLK != 7 || a.act == 12345)) {
-                if constexpr (ABLK == 8) *reinterpret_cast<u32x4*>(a.y + static_cast<size_t>(m) * a.ldy + n) = v[it];
-                else __builtin_nontemporal_store(v[it], reinterpret_cast<u32x4*>(a.y + static_cast<size_t>(m) * a.ldy + n));
+                __builtin_nontemporal_store(v[it], reinterpret_cast<u32x4*>(a.y + static_cast<size_t>(m) * a.ldy + n));
             }
         }
     }
@@ -2188,12 +1724,10 @@ struct WrConfig {
 // answers MIXQ_EINVAL for nibble-packed operands.
 #define MIXQ_WR8(MBv, WNBv, NS, Dv, LD, TAG)                                                                            \
     { "wr" TAG, MBv, WNBv, NS, LD, gemm_wreg_kernel<MBv, WNBv, NS, Dv, 0, LD, 0>, nullptr, nullptr, 0 }
-// ... and with the FP6 form (Q = 3: the weight ring held as operand tuples; 20.9 vs 22.1 us at the metric shape against Q = 2, which
-// assembles the tuples in front of each k-step's first MFMA and stays as a tuning config): X ring of NS6 stages (12 KiB each at 128 rows), weight ring of D6 k-steps: 2 for the 128-row tiles (a k-step
+// ... and with the FP6 form (Q = 3: the weight ring held as operand tuples; 20.9 vs 22.1 us at the metric shape against the first FP6 form, which
+// assembled the tuples with v_mov in front of each k-step's first MFMA - retired): X ring of NS6 stages (12 KiB each at 128 rows), weight ring of D6 k-steps: 2 for the 128-row tiles (a k-step
 // is 128 elements, twice the time of an int8 one; 3 deep is 2.7 % slower - 22.03 vs 22.68 us at the metric shape), 3 for the 64-row
-// tiles, whose k-steps are half as long (64 x 128 at 11008 -> 4096: 24.7 us with 3 or 4, 28.9 with 2; at 4096 -> 4096 12.6 / 12.9 / 13.5 us with 2 / 3 / 4): 3.  Tried and dropped: assembling the
-// tuples of k-step kt+1 DURING k-step kt into a second tuple set (two ring slots + two sets, the 9 moves spread behind MFMAs instead of
-// sitting in front of the first one): 24.5 vs 22.5 us, and wrong results on the 64-row tiles.
+// tiles, whose k-steps are half as long (64 x 128 at 11008 -> 4096: 24.7 us with 3 or 4, 28.9 with 2; at 4096 -> 4096 12.6 / 12.9 / 13.5 us with 2 / 3 / 4): 3.
 #define MIXQ_WR6(MBv, WNBv, NS, Dv, LD, NS6, D6, TAG)                                                                   \
     { "wr" TAG, MBv, WNBv, NS, LD, gemm_wreg_kernel<MBv, WNBv, NS, Dv, 0, LD, 0>,                                       \
       gemm_wreg_kernel<MBv, WNBv, NS, ((Dv) > 4 ? 4 : (Dv)) - ((MBv) * (WNBv) >= 32 ? 1 : 0), 1, LD, 0>,                \
@@ -2236,50 +1770,13 @@ const WrConfig g_wr[] = {
     // 15 (WR_KSPLIT): two workgroups per tile, half of K each (pairwise split-K).  Correct, tested, and slower than the data-parallel tilings at
     // every shape it was built for (32.6 vs 28.8 us at 11008 -> 4096, profiles/r03_splitk_ab.txt): round 5 moved it out of the product library
     MIXQ_WR(8, 2, 16, 4, 2, 50, "128x128_s16_d4_l2_k2"),
-#ifndef MIXQ_TUNING_ONLY_77                            // (-DMIXQ_TUNING_ONLY_77: a quick build for iterating on probe 77 - the split-K entry, whose index is referenced, and that probe only)
-    // ablation forms (results are garbage by design)
-    { "wr128x192_f6_abl1_noW", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 2, 2, 1>, 8 },   // the FP6 form's feed ablations
-    { "wr128x192_f6_abl2_noX", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 2, 2, 2>, 8 },
-    { "wr128x192_f6_abl3_mfma", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 2, 2, 3>, 8 },
-    { "wr128x192_f6_s10", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 10, 2, 2, 2, 0>, 10 },         // deeper X ring (Q = 2)
-    { "wr128x192_f6mov_d2", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 2, 2, 0>, 8 },         // Q = 2: tuples assembled by v_mov in front of each k-step (the first FP6 form)
-    { "wr64x128_f6mov_d3", 4, 2, 16, 2, nullptr, nullptr, gemm_wreg_kernel<4, 2, 12, 3, 2, 2, 0>, 12 },
-    { "wr128x192_f6r_d3", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 3, 3, 2, 0>, 8 },           // Q = 3 ring variants
-    { "wr128x192_f6r_s10", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 10, 2, 3, 2, 0>, 10 },
-    { "wr128x192_f6_l4", 8, 3, 16, 4, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 2, 4, 0>, 8 },            // four loader waves
-    // round 6: the tuple-ring (shipped) form's feed ablations with pseudo-random stand-ins, ring variants, and the in-k-step timeline
-    { "wr128x192_f6r_abl1_noW", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 3, 2, 1>, 8 },
+    // ablation forms (results are garbage by design) and the stamped forms of the in-k-step timeline (results are correct)
+    { "wr128x192_f6r_abl1_noW", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 3, 2, 1>, 8 },   // the FP6 form's feed ablations (pseudo-random stand-ins)
     { "wr128x192_f6r_abl2_noX", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 3, 2, 2>, 8 },
     { "wr128x192_f6r_abl3_mfma", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 3, 2, 3>, 8 },
-    { "wr128x192_f6r_abl6_nobar", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 3, 2, 6>, 8 },
-    { "wr128x192_f6r_abl32_dma_noreads", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 3, 2, 32>, 8 },
-    { "wr128x192_f6r_abl33_reads_nodma", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 3, 2, 33>, 8 },
     { "wr128x192_f6r_t36_kstep_timeline", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 3, 2, 36>, 8 },
-#define MIXQ_F6R_FL(NAME, BITS) { "wr128x192_f6r_" NAME, 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 3, 2, 100 + (BITS)>, 8 }
-    MIXQ_F6R_FL("oldswz", 128), MIXQ_F6R_FL("pace", 2), MIXQ_F6R_FL("delay", 4), MIXQ_F6R_FL("xr8_pace", 1 + 2), MIXQ_F6R_FL("xr8_delay", 1 + 4), MIXQ_F6R_FL("lprio0", 8),
-    MIXQ_F6R_FL("cprio3", 16), MIXQ_F6R_FL("xr8_lprio0", 1 + 8), MIXQ_F6R_FL("pace_lprio0", 2 + 8), MIXQ_F6R_FL("xr8_pace_lprio0", 1 + 2 + 8),
-    MIXQ_F6R_FL("xw1", 256), MIXQ_F6R_FL("xw2", 512), MIXQ_F6R_FL("xw4", 768), MIXQ_F6R_FL("t_xw1", 32 + 256), MIXQ_F6R_FL("t_xw4", 32 + 768),
-    MIXQ_F6R_FL("t_wave2", 32 + 64), MIXQ_F6R_FL("t_xr8", 32 + 1), MIXQ_F6R_FL("t_pace", 32 + 2), MIXQ_F6R_FL("t_xr8_pace", 32 + 1 + 2),
+    { "wr128x192_f6r_t_wave2", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 3, 2, 100 + 32 + 64>, 8 },
     MIXQ_WR(8, 3, 16, 4, 2, 36, "128x192_t36_kstep_timeline"), MIXQ_WR(8, 3, 16, 4, 2, 100 + 32 + 64, "128x192_t_wave2"),   // the int8 loop's in-k-step timeline
-    { "wr128x192_f6r_xr8", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 3, 2, 38>, 8 },
-    { "wr128x192_f6r_xr2", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 3, 2, 39>, 8 },
-    { "wr128x192_f6r_l4", 8, 3, 16, 4, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 2, 3, 4, 0>, 8 },
-    { "wr128x192_f6r_d4", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 8, 4, 3, 2, 0>, 8 },
-    { "wr128x192_f6r_s6", 8, 3, 16, 2, nullptr, nullptr, gemm_wreg_kernel<8, 3, 6, 2, 3, 2, 0>, 6 },
-    MIXQ_WR(8, 3, 16, 4, 2, 61, "128x192_p61_epi2_copy_at_end"),
-    MIXQ_WR(8, 3, 16, 4, 2, 62, "128x192_p62_epi2_loaders_prio0"),
-    MIXQ_WR(8, 3, 16, 4, 2, 6, "128x192_abl6_no_kloop_barriers"),   // (timing probe: what the per-k-step barrier costs; results are garbage)
-    MIXQ_WR(8, 3, 16, 4, 2, 64, "128x192_p64_epi2_no_tail_mfma"),
-    MIXQ_WR(8, 3, 16, 4, 2, 65, "128x192_p65_epi2_no_staging_writes"),
-    MIXQ_WR(8, 3, 16, 4, 2, 66, "128x192_p66_epi2_no_scaling"),
-    { "wr128x192_p70_touch", 8, 3, 16, 2, gemm_wreg_kernel<8, 3, 16, 4, 0, 2, 70>, nullptr, nullptr, 0 },   // probe: the loaders pull the panel's weight lines into L2 ahead of the consumers
-    MIXQ_WR(8, 3, 16, 4, 2, 67, "128x192_p67_epi2_loaders_copy_3_of_4"),
-#endif
-    MIXQ_WR(8, 3, 16, 4, 2, 77, "128x192_p77_one_launch"),
-#ifndef MIXQ_TUNING_ONLY_77
-    { "wr128x256_p78_mfma32x32x32", 8, 4, 16, 2, gemm_wreg_kernel<8, 4, 16, 3, 0, 2, 78>, nullptr, nullptr, 0 }, { "wr128x256_p79_shadow_acc", 8, 4, 16, 2, gemm_wreg_kernel<8, 4, 16, 3, 0, 2, 79>, nullptr, nullptr, 0 },
-    MIXQ_WR(8, 3, 8, 4, 2, 0, "128x192_s8_d4_l2"), MIXQ_WR(8, 3, 8, 4, 2, 76, "128x192_s8_p76_weights_through_lds"),
-    MIXQ_WR(8, 3, 16, 4, 2, 73, "128x192_p73_xwait_every4"), MIXQ_WR(8, 3, 16, 4, 2, 74, "128x192_p74_xwait_every2"), MIXQ_WR(8, 3, 16, 4, 2, 75, "128x192_p75_xwait_every1"),
     MIXQ_WR(8, 3, 16, 4, 2, 60, "128x192_p60_epi1"),   // cfg 0 with the first form of the epilogue (round 3's): the A/B partner of EPI2
     MIXQ_WR(8, 3, 16, 4, 2, 1, "128x192_abl1_noW"),    // cfg 0 without the weight loads
     MIXQ_WR(8, 3, 16, 4, 2, 2, "128x192_abl2_noX"),    // cfg 0 without X traffic
@@ -2288,32 +1785,7 @@ const WrConfig g_wr[] = {
     MIXQ_WR(8, 3, 16, 4, 2, 17, "128x192_abl17_noX_rnd"),
     MIXQ_WR(8, 3, 16, 4, 2, 18, "128x192_abl18_noW_rnd"),
     MIXQ_WR(8, 3, 16, 4, 2, 7, "128x192_abl7_nostore"),// cfg 0 without the stores of Y
-    MIXQ_WR(8, 3, 16, 4, 2, 8, "128x192_abl8_plainst"),// cfg 0 with ordinary (not nt) stores of Y
     MIXQ_WR(8, 3, 16, 4, 2, 9, "128x192_abl9_empty"),  // returns at entry: the launch floor of this grid and LDS footprint
-    MIXQ_WR(8, 3, 16, 4, 2, 12, "128x192_abl12_noramp"),// cfg 0 with all LOOK stages requested at once (the form before the ramp)
-    MIXQ_WR(8, 3, 16, 4, 2, 20, "128x192_p20_wlate"),  // probes of WHEN requests are issued inside a k-step (results are correct)
-    MIXQ_WR(8, 3, 16, 4, 2, 21, "128x192_p21_wearly"),
-    MIXQ_WR(8, 3, 16, 4, 2, 22, "128x192_p22_paced"),
-    MIXQ_WR(8, 3, 16, 4, 2, 23, "128x192_p23_wlate_paced"),
-    MIXQ_WR(8, 3, 16, 4, 2, 24, "128x192_p24_paced2"),
-    MIXQ_WR(8, 3, 16, 4, 2, 28, "128x192_p28_prio"),
-    MIXQ_WR(8, 3, 16, 4, 2, 41, "128x192_p41_wrapload"),
-    MIXQ_WR(8, 3, 16, 4, 2, 31, "128x192_p31_r2order"),   // round 2's order: re-read and weight load in the same gap
-    MIXQ_WR(8, 3, 16, 5, 2, 0, "128x192_s16_d5_l2"),
-    MIXQ_WR8(8, 3, 16, 6, 2, "128x192_s16_d6_l2"),        // (deeper weight rings for the cold-weights protocol: tools/trace_gemm.py --cold 8)
-    MIXQ_WR8(8, 3, 12, 6, 2, "128x192_s12_d6_l2"),
-    MIXQ_WR(8, 3, 16, 4, 4, 0, "128x192_s16_d4_l4"),
-    MIXQ_WR(8, 3, 16, 4, 2, 25, "128x192_p25_w0first"),
-    MIXQ_WR(8, 3, 16, 4, 2, 26, "128x192_p26_w0x0first"),
-    MIXQ_WR(8, 3, 16, 4, 2, 27, "128x192_p27_w0x0first_long"),
-    // EXPERIMENT (round 3, kept for the record, not shipped): the vendor library's prefill shape - 256 x 256 tiles, four fat
-    // self-loading waves with 256 accumulator registers each (SELF form of the kernel), (16 + 16) KB of operands per k-step for
-    // 4 x 64 MFMAs, half the L1 / L2 bytes per MFMA of 128 x 256.  Measured at 4096 x 11008 x 4096 without outlier columns: 186.1 us
-    // against 191.3 us for 128 x 256 (profiles/r03_prefill_ab.txt) - the loop is not feed-bound there, the part is at its 1.4 kW
-    // power cap either way - and its one-register-set tail costs 33 us with 41 outlier columns.  Known fault: memory access
-    // violation at M = 8192 and with > 64 outlier columns.  int8 only.
-    { "wr256x256_s6_d3_self", 16, 4, 6, 0, gemm_wreg_kernel<16, 4, 6, 3, 0, 0, 0>, nullptr, nullptr, 0 },
-#endif
 #endif
 };
 constexpr int WR_KSPLIT = 15;
@@ -2460,19 +1932,6 @@ bool mixq_wr_split(int bit, int M, int N, int KB, int c, int* n1, int* c2)
     return true;
 }
 
-#ifdef MIXQ_TUNING
-// mixq_gemm_set_fuse_probe (timing probe 77): the stand-in quantise phase's input rows, scratch output and counters (2 x tiles_m words, zero), until cleared
-static thread_local const uint16_t* t_fx = nullptr;
-static thread_local uint8_t* t_fq = nullptr;
-static thread_local unsigned int* t_fcnt = nullptr;
-static thread_local int t_fK = 0;
-void mixq_wr_fuse_probe(const void* x, void* scratch, void* counters, int K) { t_fx = static_cast<const uint16_t*>(x); t_fq = static_cast<uint8_t*>(scratch); t_fcnt = static_cast<unsigned int*>(counters); t_fK = K; }
-// mixq_gemm_hint_next_weights (experiment): the image the launch AFTER the next one will stream, for the next launch's loader waves to touch
-// (see the loader).  Per host thread, consumed by the next weights-in-registers launch from it.
-static thread_local const uint8_t* t_next_w = nullptr;
-static thread_local long long t_next_bytes = 0;
-void mixq_wr_hint_next(const void* w, long long bytes) { t_next_w = static_cast<const uint8_t*>(w); t_next_bytes = w && bytes > 0 ? bytes : 0; if (!t_next_bytes) t_next_w = nullptr; }
-#endif
 
 // bit: 8, 4 (nibble-packed operands) or 6 (int4 as FP6 codes, MIXQ_FMT_F6X128 operands; KB is K / 2 as for bit 4)
 int mixq_wr_launch(int c, int bit, const void* q_x, const void* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
@@ -2510,14 +1969,6 @@ int mixq_wr_launch(int c, int bit, const void* q_x, const void* q_w, const uint1
     }
     a.trace = trace;
     a.row_amax = row_amax; a.amax_mask = amax_mask;
-#ifdef MIXQ_TUNING
-    if (t_next_w && g.loaders && c != WR_KSPLIT) {
-        static const int mode = [] { const char* e = getenv("MIXQ_PF_MODE"); return e ? atoi(e) : 2; }();
-        a.pf = t_next_w; a.pf_lines = static_cast<unsigned int>(t_next_bytes >> 7); a.pf_mode = mode;
-    }
-    t_next_w = nullptr; t_next_bytes = 0;                                    // (a hint serves ONE launch)
-    if (t_fx && t_fq && t_fcnt && t_fK > 0 && (t_fK & 7) == 0 && n_begin == 0 && n_cols == N) { static const int ff = [] { const char* e = getenv("MIXQ_FUSE_FLAGS"); return e ? atoi(e) : 0; }(); a.fx = t_fx; a.fq = t_fq; a.fcnt = t_fcnt; a.fK = t_fK; a.fflags = ff; }
-#endif
     void (*k)(const WrArgs) = pair ? (bit == 8 ? g.k8p : g.k6p) : (bit == 8 ? g.k8 : (bit == 6 ? g.k6 : g.k4));
     const void* kh = bf16 ? mixq_wr_bf16_kernel(bit, c) : reinterpret_cast<const void*>(k);     // (the bf16 forms live in gemm_wreg_bf16.hip's code object)
     if (!kh) return MIXQ_EINVAL;
@@ -2531,12 +1982,8 @@ int mixq_wr_launch(int c, int bit, const void* q_x, const void* q_w, const uint1
         a.ks_slots = static_cast<uint8_t*>(ws) + fb;
         units *= 2;
     }                                                  // (the prefill tiles have no nibble form, few tilings an FP6 form)
-    const size_t ring = (bit == 6 ? static_cast<size_t>(g.nstage6) * g.mb * 1536 + 4 * g.mb * 1024 : static_cast<size_t>(g.nstage + (g.loaders ? 2 : 0)) * g.mb * 1024) + 64 /* panel flags */ + static_cast<size_t>(bm) * 4 + static_cast<size_t>(bn) * 8 /* scales */, stg = ((static_cast<size_t>(bm) * (bn * 2 + 16) + 15) & ~static_cast<size_t>(15)) + 16 * bm * 4;   // ring + the tail's X_out blocks | staging tile + row-maximum slots
-#ifdef MIXQ_TUNING
-    const size_t shm0 = ring > stg ? ring : stg, shm = shm0 + static_cast<size_t>(bn) * 64 <= 160 * 1024 ? shm0 + static_cast<size_t>(bn) * 64 : shm0;   // (room for probe 76's weight blocks where it fits)
-#else
+    const size_t ring = (bit == 6 ? static_cast<size_t>(g.nstage6) * g.mb * 1536 + 4 * g.mb * 1024 : static_cast<size_t>(g.nstage + 2) * g.mb * 1024) + 64 /* panel flags */ + static_cast<size_t>(bm) * 4 + static_cast<size_t>(bn) * 8 /* scales */, stg = ((static_cast<size_t>(bm) * (bn * 2 + 16) + 15) & ~static_cast<size_t>(15)) + 16 * bm * 4;   // ring + the tail's X_out blocks | staging tile + row-maximum slots
     const size_t shm = ring > stg ? ring : stg;
-#endif
     if (int rc = mixq_ensure_dynamic_lds(kh, shm)) return rc;
     if (bf16) {
         void* params[] = {&a};
