@@ -23,6 +23,22 @@
  *       y[m,n]     = fp16( float(acc_i32) * float(x_scale[m]) * float(scale_col[n])
  *                          + sum_j x_out[m,j]*w_out[n,j] (fp32 accumulate)  + addend[m,n] )  -> optional SiLU
  *                          -> + bias[n]; ONE rounding to fp16 at the end.
+ *
+ * Alignment and strides (what the entry points check before any launch, and what tests/test_gpu_strides.py runs)
+ *   Row strides are free parameters within the bounds each function states: ldy >= N (N / 2 for MIXQ_ACT_SILU_PAIR) and ldy % 4 == 0;
+ *   lda = 0 (one row broadcast) or lda >= N; ldxo, ldwo >= roundup(n_out,16), % 8 == 0, and independent of each other; ldx >= K
+ *   (ldx % 8 == 0 where the function says so); ldo / ldout / ldxo of the quantise side as each function states.  An output may be a
+ *   column slice of a wider buffer (y = base + column offset, ldy = the buffer's row length): nothing outside [0,M) x [0,N) of the
+ *   window is written, and the columns N..ldy-1 of a row are never touched.
+ *   Pointers (MIXQ_EINVAL otherwise; the fused GEMMs, mixq_linear_forward and mixq_dequant alike):
+ *     y, addend (and the MIXQ_ACT_SILU_MUL multiplier)   8-byte aligned: they move as 8-byte pieces.  With N % 8 == 0, ldy % 8 == 0 AND y
+ *                                                        16-byte aligned the tile leaves as 16-byte row stores; every other combination
+ *                                                        takes 8-byte stores - same arithmetic, same bytes.
+ *     x_out, w_out                                       16-byte aligned (16-byte chunks of a row)
+ *     bias, x_scale, scale_col                           2 bytes, the natural alignment of an fp16 array: they are read in groups of four
+ *                                                        through a vector type declared 2-byte aligned
+ *     mixq_gemm_i8: y32                                  16-byte aligned (four int32 leave as one store); mixq_dequant reads y32 at 4 bytes
+ *   mixq_gemm_w8a16 states its own (x 16 bytes, y 8 bytes).
  */
 #ifndef MIXQ_HIP_H
 #define MIXQ_HIP_H
@@ -227,7 +243,8 @@ int mixq_dequant_weight_cols(const void* w, const uint16_t* scale_col, const int
  *   addend fp16 [M,lda] or NULL;  bias fp16 [N] or NULL;  y fp16 [M,ldy]
  *   layout  MIXQ_X_PACKED | MIXQ_W_PACKED bits (0 = both operands plain row-major as in the reference), or
  *           MIXQ_X_PACKED | MIXQ_W_F16X64 (the weights-in-registers kernels: fragment-order weights, P16X64 activations)
- *   K % 64 == 0, N % 4 == 0, ldy % 4 == 0.
+ *   K % 64 == 0, N % 4 == 0, ldy % 4 == 0, ldy >= N, lda = 0 or >= N; y and addend 8-byte aligned, x_out and w_out 16-byte aligned,
+ *   bias 2-byte aligned ("Alignment and strides" above; MIXQ_EINVAL before any launch otherwise).
  */
 int mixq_gemm_i8_fused(const int8_t* q_x, const int8_t* q_w, const uint16_t* x_scale,
                        const uint16_t* scale_col, const uint16_t* x_out, int ldxo,
@@ -333,6 +350,8 @@ int mixq_unpack_operand(const void* src, void* dst, int R, int KB, int fmt, mixq
 /* ---- unfused debug pair ---------------------------------------------------------------------------------
  * mixq_gemm_i8 replaces mixlib.gemm(q_x, q_w, M, N, K) -> int32 [M,N]        (linear.py:235,321)
  * mixq_dequant replaces mixlib.dequantizeInt8[Silu](y32, x_scale, scale_col, addend, bit, M, N) (linear.py:238,241,324,327)
+ *   ldy (of either function), ldy32 >= N and lda (0 or any stride) are independent; mixq_gemm_i8: y32 16-byte aligned, ldy % 4 == 0;
+ *   mixq_dequant: y and addend 8-byte aligned, y32 4-byte aligned (MIXQ_EINVAL otherwise).
  */
 int mixq_gemm_i8(const int8_t* q_x, const int8_t* q_w, int32_t* y32, int ldy, int M, int N, int K,
                  mixq_stream_t stream);
@@ -403,6 +422,8 @@ int mixq_gemm_set_config(int cfg);
  * shapes it applies to).  Returns 1 and writes the first range's width and the second tiling's id when (M, N, K, bit, fmt) is split,
  * else 0. */
 int mixq_gemm_pick_split(int M, int N, int K, int bit, int fmt, int* n1, int* cfg2);
+/* The same answer for the _bf16 entry points, which pick among the tilings that have a bf16 form and split when both tilings have one. */
+int mixq_gemm_pick_split_bf16(int M, int N, int K, int bit, int fmt, int* n1, int* cfg2);
 /* Launch geometry of the extract + scale + quantise pass (mixq_quant_fused / mixq_find_row_scale): -1 automatic, 0 the
  * one-row-per-256-thread-workgroup kernel, 1..9 (threads per row, rows per workgroup) = (64,1) (64,2) (64,4) (128,1)
  * (128,2) (256,1) (256,2) (512,1) (512,2).  Every geometry produces identical bytes.  Per device, like mixq_gemm_set_config. */

@@ -82,6 +82,7 @@ SIGNATURES = {
     "mixq_gemm_pick_config": [_I, _I, _I, _I],
     "mixq_gemm_pick_config_fmt": [_I, _I, _I, _I, _I],
     "mixq_gemm_pick_split": [_I, _I, _I, _I, _I, _P, _P],
+    "mixq_gemm_pick_split_bf16": [_I, _I, _I, _I, _I, _P, _P],
     "mixq_rmsnorm": [_P, _P, _P, _I, _I, _I, _I, _F, _P],
     "mixq_rmsnorm_quant_fused": [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _F, _I, _P],
     "mixq_rmsnorm_quant_fused_masked": [_P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _F, _I, _P],
@@ -207,14 +208,15 @@ def w8a16_config_names():
     return out
 
 
-def gemm_split_plan(M, N, K, bit=8, fmt=2):
+def gemm_split_plan(M, N, K, bit=8, fmt=2, bf16=False):
     """(width of the first launch's column range, name of the second launch's tiling) when the automatic choice splits (M, N, K) along N
-    (include/mixq_hip.h: mixq_gemm_pick_split), else None."""
+    (include/mixq_hip.h: mixq_gemm_pick_split; bf16: the `_bf16` entry points' own plan, mixq_gemm_pick_split_bf16), else None."""
     lib = load()
     n1, c2 = C.c_int(0), C.c_int(-1)
-    rc = lib.mixq_gemm_pick_split(M, N, K, bit, fmt, C.byref(n1), C.byref(c2))
+    name = "mixq_gemm_pick_split_bf16" if bf16 else "mixq_gemm_pick_split"
+    rc = getattr(lib, name)(M, N, K, bit, fmt, C.byref(n1), C.byref(c2))
     if rc < 0:
-        raise RuntimeError(f"mixq_gemm_pick_split: status {rc}")
+        raise RuntimeError(f"{name}: status {rc}")
     return (n1.value, gemm_config_names()[c2.value]) if rc == 1 else None
 
 

@@ -21,6 +21,16 @@ typedef uint32_t u32x4  __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2  __attribute__((ext_vector_type(2)));
 typedef u32x2 u32x2_u __attribute__((aligned(2)));   // fp16-aligned access to 4 halves
 
+// Pointer alignment of the fused GEMMs' 16-bit operands (include/mixq_hip.h, "Alignment and strides"): y leaves as 8-byte pieces (16-byte
+// ones when the whole layout allows), the addend / multiplier arrives as 8-byte pieces, the outlier operands as 16-byte chunks; bias (and
+// the scales) are read through a 2-byte-aligned vector type, so an fp16 array's natural alignment is enough.  Checked before any launch.
+inline bool mixq_fused_pointers_aligned(const uint16_t* x_out, const uint16_t* w_out, int n_out, const uint16_t* addend, const uint16_t* bias, const uint16_t* y)
+{
+    if ((reinterpret_cast<uintptr_t>(y) & 7) || (reinterpret_cast<uintptr_t>(addend) & 7) || (reinterpret_cast<uintptr_t>(bias) & 1)) return false;
+    if (n_out > 0 && x_out && w_out && ((reinterpret_cast<uintptr_t>(x_out) | reinterpret_cast<uintptr_t>(w_out)) & 15)) return false;
+    return true;
+}
+
 #define MIXQ_WAVE 64
 
 static inline hipStream_t mixq_stream(mixq_stream_t s) { return reinterpret_cast<hipStream_t>(s); }

@@ -26,6 +26,8 @@ static int linear_forward(const mixq_linear_args* a, mixq_stream_t stream)
     if (a->wfmt == MIXQ_FMT_F16X64 && a->qfmt != MIXQ_FMT_P16X64) return MIXQ_EINVAL;
     const bool outl = a->n_cap > 0 && a->x_out && a->w_out;
     if (a->n_cap > 0 && !outl) return MIXQ_EINVAL;                  // known outlier columns need both operands of the tail
+    // the GEMM's pointer alignment (include/mixq_hip.h, "Alignment and strides"), said before the quantise pass runs
+    if (!mixq_fused_pointers_aligned(a->x_out, a->w_out, outl ? a->n_cap : 0, a->addend, a->bias, a->y)) return MIXQ_EINVAL;
     int rc = a->row_amax
         ? (BF ? mixq_quant_known_amax_bf16 : mixq_quant_known_amax)(a->x, a->ind, a->n_cap, a->n_dev, a->row_amax, a->col_mask, a->col_mask_words, a->x_scale, a->q_x, a->x_out, a->flag, a->M,
                                 a->K, a->ldx, a->ldxo, a->bit, a->sigma, a->qfmt, stream)

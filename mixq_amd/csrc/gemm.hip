@@ -899,6 +899,7 @@ int gemm_fused_common(const void* q_x, const void* q_w, const uint16_t* x_scale,
         const int need = (n_out + 15) & ~15;
         if (ldxo < need || ldwo < need || (ldxo & 7) || (ldwo & 7)) return MIXQ_ESHAPE;
     }
+    if (!mixq_fused_pointers_aligned(x_out, w_out, n_out, addend, bias, y)) return MIXQ_EINVAL;
     if (M == 0 || N == 0) return MIXQ_OK;
     GemmArgs a;
     memset(&a, 0, sizeof(a));
@@ -1008,6 +1009,7 @@ int gemm_fused_bf16(const void* q_x, const void* q_w, const uint16_t* x_scale, c
         const int need = (n_out + 15) & ~15;
         if (ldxo < need || ldwo < need || (ldxo & 7) || (ldwo & 7)) return MIXQ_ESHAPE;
     }
+    if (!mixq_fused_pointers_aligned(x_out, w_out, n_out, addend, bias, y)) return MIXQ_EINVAL;
     const int wbit = f6 ? 6 : 8;
     const int wr0 = NUM_CFGS + mixq_sk_num_configs() + 1;
     const int g_forced = g_forced_cfg.get();                     // this device's forced configuration (-1: automatic)
@@ -1107,6 +1109,7 @@ extern "C" int mixq_gemm_i8(const int8_t* q_x, const int8_t* q_w, int32_t* y32, 
 {
     if (M < 0 || N < 0 || K <= 0 || (M > 0 && N > 0 && (!q_x || !q_w || !y32))) return MIXQ_EINVAL;
     if ((K % 64) || (N & 3) || (ldy & 3) || ldy < N) return MIXQ_ESHAPE;
+    if (reinterpret_cast<uintptr_t>(y32) & 15) return MIXQ_EINVAL;           // (four int32 leave as one 16-byte store: include/mixq_hip.h, "Alignment and strides")
     if (M == 0 || N == 0) return MIXQ_OK;
     GemmArgs a;
     memset(&a, 0, sizeof(a));
@@ -1122,6 +1125,8 @@ extern "C" int mixq_dequant(const int32_t* y32, int ldy32, const uint16_t* x_sca
 {
     if (!y32 || !x_scale || !scale_col || !y || M < 0 || N < 0 || ldy32 < N || ldy < N) return MIXQ_EINVAL;
     if (act != MIXQ_ACT_NONE && act != MIXQ_ACT_SILU) return MIXQ_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(y) & 7) || (reinterpret_cast<uintptr_t>(addend) & 7) || (reinterpret_cast<uintptr_t>(y32) & 3) ||
+        (reinterpret_cast<uintptr_t>(bias) & 1)) return MIXQ_EINVAL;                  // (include/mixq_hip.h, "Alignment and strides")
     if (M == 0 || N == 0) return MIXQ_OK;
     const bool vec = (N % 8 == 0) && (ldy32 % 4 == 0) && (ldy % 8 == 0) && (!addend || lda % 8 == 0 || lda == 0) &&
                      ((reinterpret_cast<uintptr_t>(y32) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(scale_col) |
@@ -1211,6 +1216,19 @@ extern "C" int mixq_gemm_pick_split(int M, int N, int K, int bit, int fmt, int* 
     if (!f6 && ((N < 8192 && mixq_skinny_applies(8, M, N, KB, true, true)) || mixq_wr_ksplit_pays(M, N, KB))) return 0;
     int c2 = -1;
     if (!mixq_wr_split(wbit, M, N, KB, mixq_wr_pick(wbit, M, N, KB), n1, &c2)) return 0;
+    *cfg2 = NUM_CFGS + mixq_sk_num_configs() + 1 + c2;
+    return 1;
+}
+// ... of the bf16 entry points: gemm_fused_bf16's own decision (its pick among the tilings with a bf16 form, no small-batch or long-K exception,
+// and a second tiling that has a bf16 form too)
+extern "C" int mixq_gemm_pick_split_bf16(int M, int N, int K, int bit, int fmt, int* n1, int* cfg2) {
+    if ((bit != 8 && bit != 4) || M <= 0 || N <= 0 || K <= 0 || !n1 || !cfg2) return MIXQ_EINVAL;
+    const bool f6 = fmt == MIXQ_FMT_F6X128 && bit == 4;
+    if (!f6 && !(fmt == MIXQ_FMT_F16X64 && bit == 8)) return 0;
+    const int KB = bit == 8 ? K : K / 2, wbit = f6 ? 6 : 8;
+    const int c = mixq_wr_pick_bf16(wbit, M, N, KB);
+    int c2 = -1;
+    if (c < 0 || !mixq_wr_split(wbit, M, N, KB, c, n1, &c2) || !mixq_wr_has_bf16(wbit, c2)) return 0;
     *cfg2 = NUM_CFGS + mixq_sk_num_configs() + 1 + c2;
     return 1;
 }

@@ -49,6 +49,24 @@ def _rows(t, what):
     return t.data_ptr(), t.stride(0)
 
 
+def _check_out(out, rows, cols, device, who):
+    """A caller's `out` reaches the kernel as data_ptr() plus stride(0): anything but a [rows, cols] window of 16-bit rows on the operands'
+    device, with a unit column stride, a row stride the stores accept (a multiple of 4 elements, at least cols) and an 8-byte aligned base
+    (include/mixq_hip.h, "Alignment and strides") would be written somewhere else, silently.  It is refused."""
+    if out.dim() != 2:
+        raise RuntimeError(f"{who}: `out` must be 2-D, got {out.dim()} dimensions")
+    if tuple(out.shape) != (rows, cols):
+        raise RuntimeError(f"{who}: `out` must have the output's shape ({rows}, {cols}), got {tuple(out.shape)}")
+    if out.device != device:
+        raise RuntimeError(f"{who}: `out` is on {out.device}, the operands on {device}")
+    if out.stride(1) != 1:
+        raise RuntimeError(f"{who}: `out` must have a contiguous last dimension (stride(1) == 1), got stride {tuple(out.stride())}")
+    if out.stride(0) % 4 or out.stride(0) < cols:
+        raise RuntimeError(f"{who}: the row stride of `out` must be a multiple of 4 elements and at least {cols}, got {out.stride(0)}")
+    if out.data_ptr() % 8:
+        raise RuntimeError(f"{who}: `out` must be 8-byte aligned")
+
+
 def _is_zero_addend(addend):
     """The reference passes MixLibCache.zeros (all zero, row stride 36864 != N) when there are no outliers.  Recognised by
     identity only (the `_mixq_all_zero` tag MixLibCache puts on it): a caller's own stride-0 broadcast addend is real data
@@ -762,6 +780,14 @@ def DequantWeightCols(q_w, scale_col, ind, bit, out=None):
     return out
 
 
+def _aligned_addend(addend):
+    """The GEMMs read the addend / multiplier as 8-byte pieces from an 8-byte aligned base (include/mixq_hip.h, "Alignment and strides"): a
+    view that starts elsewhere goes through a contiguous copy, as a misaligned x_out does."""
+    if addend.dim() == 2 and addend.stride(1) == 1 and addend.data_ptr() % 8:
+        return addend.contiguous() if not addend.is_contiguous() else addend.clone()
+    return addend
+
+
 PAIR_LAUNCH = True                       # FusedLinear serves ACT_SILU_PAIR (fused.MixLlamaMLP asks before taking its joint gate / up route)
 
 
@@ -806,6 +832,8 @@ def FusedLinear(q_x, q_w, x_scale, scale_col, x_out, w_out, n_out, bias, M, N, K
         raise RuntimeError("FusedLinear: ACT_SILU_PAIR (the joint gate / up launch) has no bfloat16 form")
     y = out if out is not None else torch.empty((M, N // 2 if act == ACT_SILU_PAIR else N), dtype=dtype, device=q_x.device)
     _check_same_dtype(dtype, "FusedLinear", out=out)
+    if out is not None:
+        _check_out(out, M, N // 2 if act == ACT_SILU_PAIR else N, q_x.device, "FusedLinear")
     if n_out and x_out is not None and w_out is not None:
         _check_same_dtype(dtype, "FusedLinear", x_out=x_out, w_out=w_out)
         xop, ldxo = _rows(x_out, "x_out")
@@ -819,7 +847,7 @@ def FusedLinear(q_x, q_w, x_scale, scale_col, x_out, w_out, n_out, bias, M, N, K
             raise RuntimeError("FusedLinear: ACT_SILU_MUL needs the multiplier in `addend`")
         _dev_check(addend)
         _check_same_dtype(dtype, "FusedLinear", addend=addend)
-        ap, lda = _rows(addend, "addend")
+        ap, lda = _rows(_aligned_addend(addend), "addend")
     elif _is_zero_addend(addend):
         ap, lda = None, 0
     else:
@@ -827,7 +855,7 @@ def FusedLinear(q_x, q_w, x_scale, scale_col, x_out, w_out, n_out, bias, M, N, K
             addend._materialize()
         _dev_check(addend)
         _check_same_dtype(dtype, "FusedLinear", addend=addend)
-        ap, lda = _rows(addend, "addend")
+        ap, lda = _rows(_aligned_addend(addend), "addend")
     if row_amax is not None:
         if bit != 8 or row_amax.numel() < M or row_amax.element_size() != 4:
             raise RuntimeError("FusedLinear: row_amax needs an int8 GEMM and a 4-byte buffer of at least M entries")
@@ -1006,6 +1034,10 @@ def W8A16Linear(x, w_packed, scale_col, bias, N, K, out=None):
         x2 = x2.contiguous()
     M = x2.shape[0]
     y = out if out is not None else torch.empty((M, N), dtype=torch.float16, device=x.device)
+    if out is not None:
+        if out.dtype != torch.float16:
+            raise RuntimeError(f"W8A16Linear: `out` must be torch.float16, got {out.dtype}")
+        _check_out(out, M, N, x.device, "W8A16Linear")
     _capi.call("mixq_gemm_w8a16", x2.data_ptr(), x2.stride(0) if M else K, w_packed.data_ptr(), scale_col.data_ptr(), _ptr(bias),
                y.data_ptr(), y.stride(0) if M else N, M, N, K, _stream())
     return y

@@ -96,13 +96,74 @@ def test_argument_validation_without_device():
     assert lib.mixq_gemm_w8a16(one, 128, one, one, None, one, 64, 4, 62, 128, None) == _capi.MIXQ_ESHAPE      # N % 4
     assert lib.mixq_gemm_w8a16(one, 100, one, one, None, one, 64, 4, 64, 128, None) == _capi.MIXQ_ESHAPE      # ldx < K
     assert lib.mixq_gemm_w8a16(C.c_void_p(8), 128, one, one, None, one, 64, 4, 64, 128, None) == _capi.MIXQ_EINVAL  # x alignment
+    assert lib.mixq_gemm_w8a16(one, 128, one, one, None, C.c_void_p(20), 64, 4, 64, 128, None) == _capi.MIXQ_EINVAL   # y alignment (8 bytes)
     assert lib.mixq_gemm_w8a16(one, 128, one, one, None, one, 64, 0, 64, 128, None) == 0                      # M = 0
     assert lib.mixq_gemm_w8a16_set_config(99) == _capi.MIXQ_EINVAL and lib.mixq_gemm_w8a16_set_config(-1) == 0
+    # pointer alignment of the fused GEMMs, fp16 and bf16 (include/mixq_hip.h, "Alignment and strides"): y and addend 8 bytes, x_out and w_out
+    # 16 bytes, bias 2 bytes - answered before any launch (M = 0 runs every argument check and launches nothing)
+    wf16 = _capi.X_PACKED | _capi.W_F16X64
+    p4, p8, p17 = C.c_void_p(20), C.c_void_p(24), C.c_void_p(17)
+
+    def fused(fn, layout, M=0, y=one, addend=None, bias=None, x_out=None, w_out=None, n_out=0, lda=64, ld=16):
+        return fn(one, one, one, one, x_out, ld, w_out, ld, n_out, None, addend, lda, bias, y, 64, M, 64, 128, 0, layout, None)
+    for fn, layout in ((lib.mixq_gemm_i8_fused, 0), (lib.mixq_gemm_i8_fused, wf16), (lib.mixq_gemm_i4_fused, 0), (lib.mixq_gemm_i4_fused, _capi.XW_F6X128),
+                       (lib.mixq_gemm_i8_fused_bf16, wf16), (lib.mixq_gemm_i4_fused_bf16, _capi.XW_F6X128)):
+        assert fused(fn, layout) == 0
+        assert fused(fn, layout, y=p8, addend=p8, bias=C.c_void_p(18), x_out=one, w_out=one, n_out=3) == 0     # 8 / 8 / 2 / 16 / 16: the contract
+        for M in (0, 4):
+            assert fused(fn, layout, M, y=p4) == _capi.MIXQ_EINVAL
+            assert fused(fn, layout, M, y=C.c_void_p(18)) == _capi.MIXQ_EINVAL
+            assert fused(fn, layout, M, addend=p4) == _capi.MIXQ_EINVAL
+            assert fused(fn, layout, M, addend=p4, lda=0) == _capi.MIXQ_EINVAL
+            assert fused(fn, layout, M, bias=p17) == _capi.MIXQ_EINVAL
+            assert fused(fn, layout, M, x_out=p8, w_out=one, n_out=3) == _capi.MIXQ_EINVAL
+            assert fused(fn, layout, M, x_out=one, w_out=p8, n_out=3) == _capi.MIXQ_EINVAL
+        assert fused(fn, layout, x_out=p8, w_out=p8, n_out=0) == 0                                            # (no outlier columns: not read)
+    for fn in (lib.mixq_gemm_i8_fused_amax, lib.mixq_gemm_i8_fused_amax_bf16):
+        amax = lambda y, addend: fn(one, one, one, one, None, 0, None, 0, 0, None, addend, 64, None, y, 64, 0, 64, 128, 0, wf16, one, None, None)
+        assert amax(one, None) == 0 and amax(p4, None) == _capi.MIXQ_EINVAL and amax(one, p4) == _capi.MIXQ_EINVAL
+    dq = lambda y32=one, addend=None, bias=None, y=one, M=0: lib.mixq_dequant(y32, 64, one, one, addend, 64, bias, y, 64, M, 64, 0, None)
+    assert dq() == 0 and dq(y=p8, addend=p8, y32=p4) == 0
+    for M in (0, 4):
+        assert dq(y=p4, M=M) == dq(addend=p4, M=M) == dq(y32=C.c_void_p(18), M=M) == dq(bias=p17, M=M) == _capi.MIXQ_EINVAL
+    # mixq_gemm_i8 writes four int32 as one 16-byte store: y32 16-byte aligned
+    assert lib.mixq_gemm_i8(one, one, one, 64, 0, 64, 128, None) == 0
+    for M in (0, 4):
+        assert lib.mixq_gemm_i8(one, one, p8, 64, M, 64, 128, None) == lib.mixq_gemm_i8(one, one, p4, 64, M, 64, 128, None) == _capi.MIXQ_EINVAL
     # the one-call forward checks its block before it launches anything
     assert lib.mixq_linear_forward(None, None) == _capi.MIXQ_EINVAL
     blk = _capi.LinearArgs()
     blk.bit = 3
     assert lib.mixq_linear_forward(C.byref(blk), None) == _capi.MIXQ_EINVAL
+    for fwd, wfmt, qfmt in ((lib.mixq_linear_forward, _capi.FMT_P16X64, _capi.FMT_P16X64), (lib.mixq_linear_forward, _capi.FMT_F16X64, _capi.FMT_P16X64),
+                            (lib.mixq_linear_forward_bf16, _capi.FMT_F16X64, _capi.FMT_P16X64)):
+        def block(M):
+            blk = _capi.LinearArgs()
+            blk.x = blk.x_scale = blk.q_x = blk.q_w = blk.scale_col = blk.y = blk.ind = blk.x_out = blk.w_out = blk.addend = blk.bias = 16
+            blk.ldx, blk.ldy, blk.lda, blk.ldxo, blk.ldwo, blk.n_cap = 128, 64, 64, 16, 16, 3
+            blk.M, blk.N, blk.K, blk.bit, blk.sigma, blk.qfmt, blk.wfmt = M, 64, 128, 8, 6.0, qfmt, wfmt
+            return blk
+        # the positive control: with every pointer aligned the block passes every argument check of the forward, of its quantise pass and of its
+        # GEMM (M = 0: all checks run, nothing is launched) - so the MIXQ_EINVAL below is the alignment check's and nothing earlier
+        assert fwd(C.byref(block(0)), None) == 0
+        for field, value in (("y", 20), ("addend", 20), ("bias", 17), ("x_out", 24), ("w_out", 24)):        # ... the GEMM's alignment included: M > 0, no pass runs
+            for M in (0, 4):
+                blk = block(M)
+                setattr(blk, field, value)
+                assert fwd(C.byref(blk), None) == _capi.MIXQ_EINVAL, (field, M)
+
+
+def test_bf16_split_plan_is_exported_and_follows_the_fp16_plan_where_every_tiling_has_a_bf16_form():
+    """mixq_gemm_pick_split_bf16: the `_bf16` entry points' own N-split decision.  Every tiling the cost model prices has a bf16 form today, so
+    at shapes outside fp16's small-batch and long-K exceptions the two plans agree; bad arguments answer MIXQ_EINVAL."""
+    lib = _capi.load()
+    n1, c2 = C.c_int(0), C.c_int(-1)
+    assert lib.mixq_gemm_pick_split_bf16(0, 64, 64, 8, 2, C.byref(n1), C.byref(c2)) == _capi.MIXQ_EINVAL
+    assert lib.mixq_gemm_pick_split_bf16(64, 64, 64, 8, 2, None, C.byref(c2)) == _capi.MIXQ_EINVAL
+    assert lib.mixq_gemm_pick_split_bf16(512, 4096, 4096, 8, _capi.FMT_P16X64, C.byref(n1), C.byref(c2)) == 0     # a layout the bf16 GEMMs do not read
+    for M, N, K, bit, fmt in ((2048, 8200, 128, 8, 2), (1024, 9224, 256, 4, 3), (4096, 11008, 4096, 8, 2), (512, 4096, 4096, 8, 2)):
+        assert _capi.gemm_split_plan(M, N, K, bit, fmt, bf16=True) == _capi.gemm_split_plan(M, N, K, bit, fmt), (M, N, K, bit)
+    assert _capi.gemm_split_plan(2048, 8200, 128, 8, 2, bf16=True) is not None
 
 
 def test_product_library_ships_no_tuning_variants():

@@ -198,13 +198,15 @@ def problem(bit, M, K, N):
 # ---- 1. the epilogue against float64 -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("bit,name", [(8, n) for n in BF16_INT8] + [(4, n) for n in BF16_FP6])
 def test_epilogue_of_every_forced_bf16_tiling_against_float64(bit, name):
-    """200 x 512 -> 1004: a partial last M tile and a partial last N tile for every tiling (N % 4 == 0, N % 64 != 0)."""
+    """200 x 512 -> 1004: a partial last M tile and a partial last N tile for every tiling (N % 4 == 0, N % 64 != 0) - 1004 % 8 == 4, so y
+    leaves as 8-byte pieces; and 200 x 512 -> 1000 (N % 8 == 0): the same partial tiles on the LDS-staged 16-byte panel stores, the path
+    every real layer takes."""
     lib = _capi.load()
     names = _capi.gemm_config_names()
-    p = problem(bit, 200, 512, 1004)
     try:
         assert lib.mixq_gemm_set_config(names.index(name)) == 0
-        sweep(p, f"W{bit} {name}")
+        sweep(problem(bit, 200, 512, 1004), f"W{bit} {name}")
+        sweep(problem(bit, 200, 512, 1000), f"W{bit} {name} 200x512->1000")
     finally:
         assert lib.mixq_gemm_set_config(-1) == 0
 

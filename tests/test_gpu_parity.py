@@ -549,6 +549,52 @@ def test_stream_k_full_epilogue_and_int4():
     lib.mixq_gemm_set_config(-1)
 
 
+def test_stream_k_every_output_layout():
+    """The stream-K kernels carry a copy of the GEMMs' store-path selector (N % 8, ldy % 8, y % 16): every layout of frames.LAYOUTS - a padded
+    row, a column slice of a wider buffer, ld % 8 == 4, an 8-byte aligned base - against the oracle, with a guard frame around y, and
+    byte-identical to the exact-fit layout (tests/test_gpu_strides.py runs the same checks on the product library's kernels)."""
+    if not _sk_configs():
+        pytest.skip("the stream-K kernels live in the tuning build (make -C mixq_amd/csrc tuning; MIXQ_TUNING_LIB=1): tools/gpu_suite.sh runs these there")
+    from frames import GUARD_ROWS, LAYOUTS, Frame, classes_possible, store_class
+    _capi.ensure_workspace(DEV)
+    lib = _capi.load()
+    try:
+        for (M, N, K, bit, n_out, bias, addend, act) in [(200, 1000, 2048, 8, 17, True, True, 0), (200, 1004, 2048, 8, 41, False, False, 1),
+                                                         (64, 256, 4096, 4, 16, True, True, 1), (1, 256, 2048, 8, 0, False, False, 0)]:
+            c = _fused_case(M, N, K, bit, seed=M + K, n_out=n_out, bias=bias, addend=addend, act=act)
+            ref = O.linear_fused(c["qx"], c["qw"], c["sx"], c["sw"], xo=c["xo"], wo=c["wo"], addend=c["addend"], bias=c["bias"], act=act, bit=bit).astype(np.float32)
+            qx, qw = mixlib.PackOperand(t(c["qx"]), 1), mixlib.PackOperand(t(c["qw"]), 1)
+            sx = torch.zeros((M, 1), dtype=torch.float16, device=DEV); sx[:, 0] = t(c["sx"])
+            pad = (n_out + 15) // 16 * 16
+            xo = wo = None
+            if n_out:
+                xo = torch.full((M, pad + 8), float("nan"), dtype=torch.float16, device=DEV); xo[:, :n_out] = t(c["xo"]); xo = xo[:, :n_out]
+                wo = torch.full((N, pad + 32), float("nan"), dtype=torch.float16, device=DEV); wo[:, :n_out] = t(c["wo"]); wo = wo[:, :n_out]
+            ad = None
+            if addend:
+                ad = torch.zeros((M, N + 4), dtype=torch.float16, device=DEV)[:, :N]
+                ad.copy_(t(c["addend"]))
+            for cfg in _sk_configs():
+                assert lib.mixq_gemm_set_config(cfg) == 0
+                first, ran = None, set()
+                for ld, col_off, elem_off in LAYOUTS(N):
+                    f = Frame(M, N, ld, col_off, elem_off, torch.float16, DEV, GUARD_ROWS)
+                    cls = store_class(N, ld, f.view.data_ptr())
+                    what = f"{_capi.gemm_config_names()[cfg]} {M}x{K}->{N} W{bit} ld={ld} col_off={col_off} elem_off={elem_off} [{cls}]"
+                    y = mixlib.FusedLinear(qx, qw, sx, t(c["sw"]), xo, wo, n_out, None if c["bias"] is None else t(c["bias"]), M, N, K, bit=bit, act=act,
+                                           addend=ad, out=f.view)
+                    got = n(y).astype(np.float32)
+                    assert np.isfinite(got).all(), what
+                    assert (np.abs(got - ref) <= ulp_tol(ref)).all(), f"{what}: {np.abs(got - ref).max()}"
+                    f.assert_untouched(what)
+                    first = y.clone() if first is None else first
+                    assert torch.equal(y, first), f"{what}: differs from the exact-fit layout"
+                    ran.add(cls)
+                assert ran == classes_possible(N)
+    finally:
+        lib.mixq_gemm_set_config(-1)
+
+
 def test_linearity_in_the_outlier_operand():
     """Y(xo1 + xo2) - Y(0) == (Y(xo1) - Y(0)) + (Y(xo2) - Y(0)) up to fp16 rounding: the fp16 MFMA tail is additive."""
     c = _fused_case(64, 128, 256, 8, seed=4, n_out=16, bias=False, addend=False, act=0)
