@@ -31,6 +31,20 @@ inline bool mixq_fused_pointers_aligned(const uint16_t* x_out, const uint16_t* w
     return true;
 }
 
+// One fused GEMM call as the host code passes it around: filled once per entry point (gemm.hip), read by the launchers of gemm_skinny.hip,
+// gemm_wreg.hip and gemm_sk.hip.  The C ABI's arguments in its order (include/mixq_hip.h, mixq_gemm_i8_fused); KB = K, or K / 2 for 4-bit values.
+struct MixqFusedProblem {
+    const void *q_x, *q_w; const uint16_t *x_scale, *scale_col;
+    const uint16_t* x_out; int ldxo;
+    const uint16_t* w_out; int ldwo;
+    int n_out; const int32_t* n_out_dev;
+    const uint16_t* addend; int lda;
+    const uint16_t* bias; uint16_t* y; int ldy;
+    int M, N, KB, act;
+    uint32_t* row_amax; const uint32_t* amax_mask;     // the row-maximum side output (mixq_gemm_i8_fused_amax), or null
+    bool bf16;                                         // x_out, w_out, addend and y are bfloat16 (the _bf16 entry points)
+};
+
 #define MIXQ_WAVE 64
 
 static inline hipStream_t mixq_stream(mixq_stream_t s) { return reinterpret_cast<hipStream_t>(s); }

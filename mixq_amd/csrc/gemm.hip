@@ -809,8 +809,6 @@ constexpr unsigned long long* g_trace = nullptr;
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// Shape-aware choice: estimated time ~ rounds over 256 CUs x max(MFMA time, feed time) per k-step of a tile.
-//   MFMA: BM*BN*64*2 ops at 8192 ops/clk/CU;  feed: (BM+BN)*64 bytes at ~48 B/clk/CU (packed) / 25 (plain rows).
 // Shape-aware choice.  Score = rounds over the 256 CUs x measured time per k-step of one tile (microseconds, MI355X,
 // packed operands, tools/sweep_gemm.py over the Llama-2-7b/70b and Llama-3-8B shapes).  The winner per
 // shape in those sweeps is what this picks: whichever tile makes close to 256 tiles wins - 64x128 at N = 4096, 64x192 at
@@ -819,8 +817,7 @@ struct PickEntry { int cfg; float tk; };
 const PickEntry g_pick[] = {{0, 0.60f}, {1, 0.39f}, {2, 0.60f}, {3, 0.40f}, {4, 0.40f}, {5, 0.40f}, {6, 0.37f}, {7, 0.40f}, {8, 0.31f},
                             {9, 0.33f}, {10, 0.26f}, {11, 0.17f}, {12, 0.15f}, {13, 0.60f}, {14, 0.40f}, {15, 0.36f}, {17, 0.165f}, {18, 0.21f}};
 constexpr int NUM_PICK = sizeof(g_pick) / sizeof(g_pick[0]);
-int pick_config(int M, int N, int KB, bool packed) {
-    (void)KB; (void)packed;
+int pick_config(int M, int N) {
     double best = 1e30; int bi = 0;
     for (int pi = 0; pi < NUM_PICK; ++pi) {
         const int c = g_pick[pi].cfg;
@@ -835,6 +832,8 @@ int pick_config(int M, int N, int KB, bool packed) {
     }
     return bi;
 }
+// the tiling of this file a launch runs: the forced one when a tiling of this file is forced, else the pick
+int lds_config(int forced, int M, int N) { return (forced >= 0 && forced < NUM_CFGS) ? forced : pick_config(M, N); }
 
 // Stream-K (gemm_sk.hip) pays when the data-parallel tiling leaves most CUs idle AND K is long: measured on MI355X
 // (tools/sweep_gemm.py), M = 512: 4096x11008 46.1 -> 39.3 us, 4096x14336 54.9 -> 43.4 us with sk128x128; at K = 4096
@@ -853,18 +852,11 @@ int pick_stream_k(int M, int N, int KB) {
     return 3;                                            // sk128x128_w2x2_s5
 }
 
-// (Rounds 3-4 preferred this file's 256 x 256 tiling - cfg LDS256 - at prefill sizes; since the weights-in-registers kernels got the
-// panel epilogue, 128 x 256 is ahead of it at every prefill shape measured, by 2.7-13 %: profiles/r05_prefill_sweep.txt.  The tiling stays
-// selectable by configuration and reads the fragment-order weight image through a remapped DMA source.)
-// (cfg 13: 256x256_w4x2_s5_l0)
-
-int launch_gemm(GemmArgs& a, int mode, hipStream_t st, int cfg = -1) {
-    const bool packed = a.x_packed && a.w_packed;
-    const int forced = g_forced_cfg.get();
-    const int c = cfg >= 0 ? cfg : ((forced >= 0 && forced < NUM_CFGS) ? forced : pick_config(a.M, a.N, a.KB, packed));
-    const GemmConfig* g = &g_cfgs[c];
-    a.tiles_m = cdiv(a.M, g->bm);
-    a.tiles_n = cdiv(a.N, g->bn);
+// (cfg 13, 256x256_w4x2_s5_l0, was rounds 3-4's prefill tiling; the weights-in-registers 128 x 256 tile is ahead of it at every prefill shape
+// measured, by 2.7-13 %: profiles/r05_prefill_sweep.txt.  It stays selectable and reads the fragment-order weight image through a remapped DMA source.)
+int launch_gemm(GemmArgs& a, int mode, hipStream_t st, int cfg) {
+    const GemmConfig* g = &g_cfgs[cfg];
+    a.tiles_m = cdiv(a.M, g->bm); a.tiles_n = cdiv(a.N, g->bn);
     a.gm = a.tiles_m <= 8 ? a.tiles_m : 8;
     a.trace = g_trace;
     void (*k)(const GemmArgs) = mode == 0 ? g->k8 : (mode == 1 ? g->k4 : g->k32);
@@ -874,159 +866,195 @@ int launch_gemm(GemmArgs& a, int mode, hipStream_t st, int cfg = -1) {
     return mixq_launch_status();
 }
 
-int gemm_fused_common(const void* q_x, const void* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
-                      const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
-                      const uint16_t* addend, int lda, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int K,
-                      int act, int layout, int bit, mixq_stream_t stream, uint32_t* row_amax = nullptr, const uint32_t* amax_mask = nullptr)
+// ---- the route of a fused call -------------------------------------------------------------------------------------------------------
+// Four kernel families serve the fused entry points.  Config ids (mixq_gemm_set_config, mixq_gemm_config_name, the pick queries) number
+// them in this order: [0, NUM_CFGS) the LDS-staged tilings of this file, then the stream-K forms (tuning build), then "decode32" (the
+// small-batch kernel of gemm_skinny.hip), then the weights-in-registers tilings of gemm_wreg.hip.
+enum RouteKind { ROUTE_LDS, ROUTE_SK, ROUTE_SKINNY, ROUTE_WR };
+int cfg_id(RouteKind kind, int c) {
+    return kind == ROUTE_LDS ? c : (kind == ROUTE_SK ? NUM_CFGS + c : NUM_CFGS + mixq_sk_num_configs() + (kind == ROUTE_SKINNY ? 0 : 1 + c));
+}
+RouteKind cfg_family(int id, int* c) {               // id >= 0
+    const int sk0 = NUM_CFGS, dec = sk0 + mixq_sk_num_configs();
+    if (id < sk0) { *c = id; return ROUTE_LDS; }
+    if (id < dec) { *c = id - sk0; return ROUTE_SK; }
+    *c = id == dec ? 0 : id - dec - 1;
+    return id == dec ? ROUTE_SKINNY : ROUTE_WR;
+}
+int total_configs() { return cfg_id(ROUTE_WR, mixq_wr_num_configs()); }
+
+// status: MIXQ_OK, or why the combination is refused (nothing else is meaningful then); cfg: the family's own index; n1 > 0: an N split -
+// tiling cfg over the weight rows [0, n1), tiling cfg2 over the rest
+struct Route { int status; RouteKind kind; int cfg, n1, cfg2; };
+
+// (a forced configuration, id >= 0, that the bf16 entry points can run: a weights-in-registers tiling with a bf16 form)
+bool forced_has_bf16(int wbit, int forced) { int c = -1; return cfg_family(forced, &c) == ROUTE_WR && mixq_wr_has_bf16(wbit, c); }
+
+// THE place where a route is decided: the fused entry points launch what this returns, the queries (mixq_gemm_pick_config_fmt,
+// mixq_gemm_pick_split[_bf16], mixq_gemm_amax_supported[_bf16]) read it with forced = -1.  `layout` is MIXQ_XW_F6X128 or a valid combination
+// of the flag bits (validate_fused), `act` decides the paired epilogue (and keeps the multiplier form off stream-K), `forced` is this device's
+// mixq_gemm_set_config value: -1 automatic, -2 automatic without the N split, else a config id.  bf16 (x_out, w_out, addend and y are
+// bfloat16; scales and bias stay fp16) is served by the weights-in-registers kernels only, at every batch size.  fp16 asks in this order:
+// FP6 codes, the small-batch kernel, fragment-order weights, stream-K, the LDS-staged kernel.
+Route plan_route(int bit, int layout, int M, int N, int KB, int act, bool want_amax, bool bf16, int forced)
 {
+    const auto refuse = [](int status) { return Route{status, ROUTE_LDS, -1, 0, -1}; };
     const bool f6 = layout == MIXQ_XW_F6X128;                    // both operands as FP6 codes: the W4A4 form on the FP6 matrix pipe
-    if (f6) { if (bit != 4) return MIXQ_EINVAL; layout = 0; }
-    if (layout & ~(MIXQ_X_PACKED | MIXQ_W_PACKED | MIXQ_W_F16X64)) return MIXQ_EINVAL;
-    if ((layout & MIXQ_W_PACKED) && (layout & MIXQ_W_F16X64)) return MIXQ_EINVAL;
-    const bool wf16 = layout & MIXQ_W_F16X64;
-    if (wf16 && !(layout & MIXQ_X_PACKED)) return MIXQ_EINVAL;   // fragment-order weights go with P16X64 activations
-    if (M < 0 || N < 0 || K <= 0 || n_out < 0) return MIXQ_EINVAL;
-    if (M > 0 && N > 0 && (!q_x || !q_w || !x_scale || !scale_col || !y)) return MIXQ_EINVAL;
-    if (act != MIXQ_ACT_NONE && act != MIXQ_ACT_SILU && act != MIXQ_ACT_SILU_MUL && act != MIXQ_ACT_SILU_PAIR) return MIXQ_EINVAL;
-    if (act == MIXQ_ACT_SILU_MUL && !addend) return MIXQ_EINVAL;            // the multiplier is mandatory
-    const bool pair = act == MIXQ_ACT_SILU_PAIR;                            // interleaved gate / up rows: y has N / 2 columns
-    if (pair && addend) return MIXQ_EINVAL;
-    if (pair && (!((bit == 8 && wf16) || f6) || (N & 15))) return MIXQ_ESHAPE;   // (the weights-in-registers kernels: int8 fragment-order weights, or FP6 codes)
-    const int KB = bit == 8 ? K : K / 2;
-    if ((KB % 64) || (bit == 4 && (K & 1)) || (N & 3) || (ldy & 3) || ldy < (pair ? N / 2 : N)) return MIXQ_ESHAPE;
-    if (addend && lda != 0 && lda < N) return MIXQ_EINVAL;
-    if (n_out > 0 && x_out && w_out) {
-        const int need = (n_out + 15) & ~15;
-        if (ldxo < need || ldwo < need || (ldxo & 7) || (ldwo & 7)) return MIXQ_ESHAPE;
+    const bool x_packed = !f6 && (layout & MIXQ_X_PACKED), w_packed = !f6 && (layout & MIXQ_W_PACKED), wf16 = !f6 && (layout & MIXQ_W_F16X64);
+    const bool pair = act == MIXQ_ACT_SILU_PAIR;
+    int fc = -1;                                                 // the forced configuration as (family, index)
+    const bool is_forced = forced >= 0;
+    const RouteKind fk = is_forced ? cfg_family(forced, &fc) : ROUTE_LDS;
+    const bool forced_wr = is_forced && fk == ROUTE_WR;
+    Route r = {MIXQ_OK, ROUTE_WR, -1, 0, -1};
+    if (bf16) {
+        const int wbit = f6 ? 6 : 8;
+        if (!f6 && !(bit == 8 && layout == (MIXQ_X_PACKED | MIXQ_W_F16X64))) return refuse(MIXQ_ESHAPE);
+        if (is_forced && !forced_has_bf16(wbit, forced)) return refuse(MIXQ_EINVAL);
+        r.cfg = is_forced ? fc : mixq_wr_pick_bf16(wbit, M, N, KB);
+        if (r.cfg < 0) return refuse(MIXQ_ESHAPE);               // (no tiling with a bf16 form serves the problem)
+        // a partial last round of tiles: two launches as for fp16, when both tilings have bf16 forms
+        if (forced == -1 && mixq_wr_split(wbit, M, N, KB, r.cfg, &r.n1, &r.cfg2) && !mixq_wr_has_bf16(wbit, r.cfg2)) r.n1 = 0;
+        return r;
     }
-    if (!mixq_fused_pointers_aligned(x_out, w_out, n_out, addend, bias, y)) return MIXQ_EINVAL;
-    if (M == 0 || N == 0) return MIXQ_OK;
-    GemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.qx = static_cast<const uint8_t*>(q_x); a.qw = static_cast<const uint8_t*>(q_w);
-    a.sx = x_scale; a.sw = scale_col; a.xo = x_out; a.wo = w_out; a.n_out_dev = n_out_dev;
-    a.addend = addend; a.bias = bias; a.y = y;
-    a.M = M; a.N = N; a.KB = KB; a.ldxo = ldxo; a.ldwo = ldwo; a.n_out = n_out; a.lda = lda; a.ldy = ldy; a.act = act;
-    a.x_packed = (layout & MIXQ_X_PACKED) ? 1 : 0; a.w_packed = (layout & MIXQ_W_PACKED) ? 1 : 0;
-    a.xrows16 = (M + 15) & ~15; a.wrows16 = (N + 15) & ~15;
-    const int sk_num = mixq_sk_num_configs();
-    const int skinny_id = NUM_CFGS + sk_num, wr0 = skinny_id + 1;
-    const int g_forced = g_forced_cfg.get();                     // this device's forced configuration (-1: automatic)
     if (f6) {
-        if (row_amax) return MIXQ_ESHAPE;
-        if (g_forced >= 0 && g_forced < wr0) return MIXQ_EINVAL;                // only the weights-in-registers kernels read this format
-        const int c = g_forced >= wr0 ? g_forced - wr0 : (pair ? mixq_wr_pick_pair(6, M, N, KB) : mixq_wr_pick(6, M, N, KB));
-        if (pair && !mixq_wr_has_pair(6, c)) return MIXQ_EINVAL;
-        int n1 = 0, c2 = -1;
-        if (g_forced == -1 && !pair && mixq_wr_split(6, M, N, KB, c, &n1, &c2)) {   // (a partial last round of tiles: two launches, as for int8 below)
-            if (int rc = mixq_wr_launch(c, 6, q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
-                                        ldy, M, N, KB, act, g_trace, mixq_stream(stream), nullptr, nullptr, 0, n1)) return rc;
-            return mixq_wr_launch(c2, 6, q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
-                                  ldy, M, N, KB, act, nullptr, mixq_stream(stream), nullptr, nullptr, n1, N - n1);
-        }
-        return mixq_wr_launch(c, 6, q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
-                              ldy, M, N, KB, act, g_trace, mixq_stream(stream), nullptr, nullptr);
+        if (want_amax) return refuse(MIXQ_ESHAPE);
+        if (is_forced && !forced_wr) return refuse(MIXQ_EINVAL);        // only the weights-in-registers kernels read this format
+        r.cfg = forced_wr ? fc : (pair ? mixq_wr_pick_pair(6, M, N, KB) : mixq_wr_pick(6, M, N, KB));
+        if (pair && !mixq_wr_has_pair(6, r.cfg)) return refuse(MIXQ_EINVAL);
+        if (forced == -1 && !pair) mixq_wr_split(6, M, N, KB, r.cfg, &r.n1, &r.cfg2);   // (a partial last round of tiles: two launches, as for int8 below)
+        return r;
     }
     // small-batch form (gemm_skinny.hip): M <= 32, packed operands (either packed layout): a weight stream, no LDS staging
-    {
-        const bool both_packed = a.x_packed && (a.w_packed || wf16);
-        // (wide layers with fragment-order int8 weights: the 32 x 64 weights-in-registers tiling streams faster, gemm_wreg.hip)
-        const bool wide_wr = wf16 && bit == 8 && N >= 8192 && g_forced < 0;
-        if (!pair && !wide_wr && (g_forced < 0 || g_forced == skinny_id) && mixq_skinny_applies(bit, M, N, KB, both_packed, both_packed)) {
-            if (row_amax) return MIXQ_ESHAPE;                    // the row-maximum side output lives in the weights-in-registers kernels
-            return mixq_skinny_launch(bit, q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
-                                      ldy, M, N, KB, act, wf16 ? 1 : 0, mixq_stream(stream));
-        }
-        if (g_forced == skinny_id && !pair) return MIXQ_EINVAL;
+    const bool both_packed = x_packed && (w_packed || wf16);
+    // (wide layers with fragment-order int8 weights: the 32 x 64 weights-in-registers tiling streams faster, gemm_wreg.hip)
+    const bool wide_wr = wf16 && bit == 8 && N >= 8192 && !is_forced;
+    const bool forced_skinny = is_forced && fk == ROUTE_SKINNY;
+    if (!pair && !wide_wr && (!is_forced || forced_skinny) && mixq_skinny_applies(bit, M, N, KB, both_packed, both_packed)) {
+        if (want_amax) return refuse(MIXQ_ESHAPE);               // the row-maximum side output lives in the weights-in-registers kernels
+        return Route{MIXQ_OK, ROUTE_SKINNY, 0, 0, -1};
     }
+    if (forced_skinny && !pair) return refuse(MIXQ_EINVAL);
     // fragment-order weights: the weights-in-registers kernels (gemm_wreg.hip); a forced tiling of this file reads the same F16X64 weight
     // image through a remapped DMA source
     if (wf16) {
-        int c;
         if (pair) {
-            c = g_forced >= wr0 ? g_forced - wr0 : mixq_wr_pick_pair(8, M, N, KB);
-            if (!mixq_wr_has_pair(8, c)) return MIXQ_EINVAL;                // (a forced tiling without the paired epilogue)
+            r.cfg = forced_wr ? fc : mixq_wr_pick_pair(8, M, N, KB);
+            if (!mixq_wr_has_pair(8, r.cfg)) return refuse(MIXQ_EINVAL);    // (a forced tiling without the paired epilogue)
         }
-        else if (g_forced >= wr0) c = g_forced - wr0;
-        else if (g_forced >= NUM_CFGS) return MIXQ_EINVAL;               // a stream-K form was forced: it takes P16X64 weights only
-        else if (g_forced >= 0) {                                          // a tiling of this file, forced: it reads the fragment-order image too
-            if (row_amax) return MIXQ_ESHAPE;
-            a.w_packed = 1; a.w_f16 = 1;
-            return launch_gemm(a, bit == 8 ? 0 : 1, mixq_stream(stream), g_forced);
+        else if (forced_wr) r.cfg = fc;
+        else if (is_forced && fk != ROUTE_LDS) return refuse(MIXQ_EINVAL);  // a stream-K form was forced: it takes P16X64 weights only
+        else if (is_forced) {                                               // a tiling of this file, forced: it reads the fragment-order image too
+            if (want_amax) return refuse(MIXQ_ESHAPE);
+            r.kind = ROUTE_LDS; r.cfg = fc;
         }
-        else if (bit == 8 && !row_amax && mixq_wr_ksplit_pays(M, N, KB)) c = mixq_wr_ksplit_config();   // long K, few tiles: two workgroups per tile
+        else if (bit == 8 && !want_amax && mixq_wr_ksplit_pays(M, N, KB)) r.cfg = mixq_wr_ksplit_config();   // long K, few tiles: two workgroups per tile
         else {
-            c = mixq_wr_pick(bit, M, N, KB);
+            r.cfg = mixq_wr_pick(bit, M, N, KB);
             // a partial last round of tiles: the full rounds' columns with this tiling, the rest with the cheapest one, two launches
-            int n1 = 0, c2 = -1;
-            if (g_forced == -1 && bit == 8 && mixq_wr_split(8, M, N, KB, c, &n1, &c2)) {
-                if (int rc = mixq_wr_launch(c, bit, q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
-                                            ldy, M, N, KB, act, g_trace, mixq_stream(stream), row_amax, amax_mask, 0, n1)) return rc;
-                return mixq_wr_launch(c2, bit, q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
-                                      ldy, M, N, KB, act, nullptr, mixq_stream(stream), row_amax, amax_mask, n1, N - n1);
-            }
+            if (forced == -1 && bit == 8) mixq_wr_split(8, M, N, KB, r.cfg, &r.n1, &r.cfg2);
         }
-        return mixq_wr_launch(c, bit, q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
-                              ldy, M, N, KB, act, g_trace, mixq_stream(stream), row_amax, amax_mask);
+        return r;
     }
-    if (row_amax) return MIXQ_ESHAPE;                            // (only the fragment-order-weights route computes it)
-    if (g_forced >= wr0) return MIXQ_EINVAL;
+    if (want_amax) return refuse(MIXQ_ESHAPE);                   // (only the fragment-order-weights route computes it)
+    if (forced_wr) return refuse(MIXQ_EINVAL);
     // stream-K form (gemm_sk.hip): packed operands, workspace registered, chosen explicitly or by the shape rule
-    if (a.x_packed && a.w_packed && act != MIXQ_ACT_SILU_MUL) {       // (the stream-K epilogue has no multiplier form)
-        int sk = -1;
-        if (g_forced >= NUM_CFGS) sk = g_forced - NUM_CFGS;
-        else if (g_forced < 0) sk = pick_stream_k(M, N, KB);
-        if (sk >= 0 && mixq_sk_usable(sk))
-            return mixq_sk_launch(sk, bit, q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda,
-                                  bias, y, ldy, M, N, KB, act, mixq_stream(stream));
+    if (x_packed && w_packed && act != MIXQ_ACT_SILU_MUL) {      // (the stream-K epilogue has no multiplier form)
+        const int sk = is_forced ? (fk == ROUTE_SK ? fc : -1) : pick_stream_k(M, N, KB);
+        if (sk >= 0 && mixq_sk_usable(sk)) { r.kind = ROUTE_SK; r.cfg = sk; return r; }
     }
-    return launch_gemm(a, bit == 8 ? 0 : 1, mixq_stream(stream));
+    r.kind = ROUTE_LDS; r.cfg = lds_config(forced, M, N);
+    return r;
 }
 
-// The bf16 forms (include/mixq_hip.h, "bf16 layers"): x_out, w_out, addend and y are bfloat16; scales and bias stay fp16.  Served by the
-// weights-in-registers kernels only - int8 as MIXQ_X_PACKED | MIXQ_W_F16X64, 4-bit as MIXQ_XW_F6X128 - at every batch size (no bf16 form of
-// this file's LDS-staged kernel or of gemm_skinny.hip): other layouts answer MIXQ_ESHAPE, a forced configuration without a bf16 form
-// MIXQ_EINVAL, both before any launch.
-int gemm_fused_bf16(const void* q_x, const void* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
-                    const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
-                    const uint16_t* addend, int lda, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int K,
-                    int act, int layout, int bit, mixq_stream_t stream, uint32_t* row_amax = nullptr, const uint32_t* amax_mask = nullptr)
+// Argument checks of the fused entry points, fp16 and bf16 container alike (p.bf16), before any launch.  The ORDER is part of the C ABI's
+// behaviour - where two faults coincide the earlier check answers: 1 layout (bf16 leaves the two F16X64 combination checks to step 5's
+// MIXQ_ESHAPE), 2 sizes, 3 null operands, 4 act and its operands, 5 what the kernels of the container serve (bf16: no paired form, then the
+// two layouts of the weights-in-registers kernels), 6 K / N / ldy shape, 7 lda, 8 outlier strides, 9 pointer alignment, 10 (bf16) a forced
+// configuration without a bf16 form - ahead of the caller's M == 0 || N == 0 early-out, which fp16's forced-configuration answers follow.
+int validate_fused(const MixqFusedProblem& p, int K, int layout, int bit, int forced)
 {
     const bool f6 = layout == MIXQ_XW_F6X128;
     if (f6 && bit != 4) return MIXQ_EINVAL;
     if (!f6 && (layout & ~(MIXQ_X_PACKED | MIXQ_W_PACKED | MIXQ_W_F16X64))) return MIXQ_EINVAL;
-    if (M < 0 || N < 0 || K <= 0 || n_out < 0) return MIXQ_EINVAL;
-    if (M > 0 && N > 0 && (!q_x || !q_w || !x_scale || !scale_col || !y)) return MIXQ_EINVAL;
-    if (act != MIXQ_ACT_NONE && act != MIXQ_ACT_SILU && act != MIXQ_ACT_SILU_MUL && act != MIXQ_ACT_SILU_PAIR) return MIXQ_EINVAL;
-    if (act == MIXQ_ACT_SILU_MUL && !addend) return MIXQ_EINVAL;            // the multiplier is mandatory
-    if (act == MIXQ_ACT_SILU_PAIR) return MIXQ_ESHAPE;                      // (the joint gate / up form is fp16 only)
-    if (!(f6 || (bit == 8 && layout == (MIXQ_X_PACKED | MIXQ_W_F16X64)))) return MIXQ_ESHAPE;
-    if (f6 && row_amax) return MIXQ_ESHAPE;
-    const int KB = bit == 8 ? K : K / 2;
-    if ((KB % 64) || (bit == 4 && (K & 1)) || (N & 3) || (ldy & 3) || ldy < N) return MIXQ_ESHAPE;
-    if (addend && lda != 0 && lda < N) return MIXQ_EINVAL;
-    if (n_out > 0 && x_out && w_out) {
-        const int need = (n_out + 15) & ~15;
-        if (ldxo < need || ldwo < need || (ldxo & 7) || (ldwo & 7)) return MIXQ_ESHAPE;
+    const bool wf16 = !f6 && (layout & MIXQ_W_F16X64);
+    if (!p.bf16 && wf16 && layout != (MIXQ_X_PACKED | MIXQ_W_F16X64)) return MIXQ_EINVAL;   // fragment-order weights: no second weight format, P16X64 activations
+    if (p.M < 0 || p.N < 0 || K <= 0 || p.n_out < 0) return MIXQ_EINVAL;
+    if (p.M > 0 && p.N > 0 && (!p.q_x || !p.q_w || !p.x_scale || !p.scale_col || !p.y)) return MIXQ_EINVAL;
+    if (p.act != MIXQ_ACT_NONE && p.act != MIXQ_ACT_SILU && p.act != MIXQ_ACT_SILU_MUL && p.act != MIXQ_ACT_SILU_PAIR) return MIXQ_EINVAL;
+    if (p.act == MIXQ_ACT_SILU_MUL && !p.addend) return MIXQ_EINVAL;        // the multiplier is mandatory
+    const bool pair = p.act == MIXQ_ACT_SILU_PAIR;                          // interleaved gate / up rows: y has N / 2 columns
+    if (p.bf16) {
+        if (pair) return MIXQ_ESHAPE;                                       // (the joint gate / up form is fp16 only)
+        if (!(f6 || (bit == 8 && layout == (MIXQ_X_PACKED | MIXQ_W_F16X64)))) return MIXQ_ESHAPE;
+        if (f6 && p.row_amax) return MIXQ_ESHAPE;
+    } else {
+        if (pair && p.addend) return MIXQ_EINVAL;
+        if (pair && (!((bit == 8 && wf16) || f6) || (p.N & 15))) return MIXQ_ESHAPE;   // (the weights-in-registers kernels: int8 fragment-order weights, or FP6 codes)
     }
-    if (!mixq_fused_pointers_aligned(x_out, w_out, n_out, addend, bias, y)) return MIXQ_EINVAL;
-    const int wbit = f6 ? 6 : 8;
-    const int wr0 = NUM_CFGS + mixq_sk_num_configs() + 1;
-    const int g_forced = g_forced_cfg.get();                     // this device's forced configuration (-1: automatic)
-    if (g_forced >= 0 && (g_forced < wr0 || !mixq_wr_has_bf16(wbit, g_forced - wr0))) return MIXQ_EINVAL;
-    if (M == 0 || N == 0) return MIXQ_OK;
-    const int c = g_forced >= 0 ? g_forced - wr0 : mixq_wr_pick_bf16(wbit, M, N, KB);
-    if (c < 0) return MIXQ_ESHAPE;                               // (no tiling with a bf16 form serves the problem)
-    int n1 = 0, c2 = -1;
-    // a partial last round of tiles: two launches as for fp16, when both tilings have bf16 forms
-    if (g_forced == -1 && mixq_wr_split(wbit, M, N, KB, c, &n1, &c2) && mixq_wr_has_bf16(wbit, c2)) {
-        if (int rc = mixq_wr_launch(c, wbit, q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
-                                    ldy, M, N, KB, act, nullptr, mixq_stream(stream), row_amax, amax_mask, 0, n1, true)) return rc;
-        return mixq_wr_launch(c2, wbit, q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
-                              ldy, M, N, KB, act, nullptr, mixq_stream(stream), row_amax, amax_mask, n1, N - n1, true);
+    if ((p.KB % 64) || (bit == 4 && (K & 1)) || (p.N & 3) || (p.ldy & 3) || p.ldy < (pair ? p.N / 2 : p.N)) return MIXQ_ESHAPE;
+    if (p.addend && p.lda != 0 && p.lda < p.N) return MIXQ_EINVAL;
+    if (p.n_out > 0 && p.x_out && p.w_out) {
+        const int need = (p.n_out + 15) & ~15;
+        if (p.ldxo < need || p.ldwo < need || (p.ldxo & 7) || (p.ldwo & 7)) return MIXQ_ESHAPE;
     }
-    return mixq_wr_launch(c, wbit, q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
-                          ldy, M, N, KB, act, nullptr, mixq_stream(stream), row_amax, amax_mask, 0, -1, true);
+    if (!mixq_fused_pointers_aligned(p.x_out, p.w_out, p.n_out, p.addend, p.bias, p.y)) return MIXQ_EINVAL;
+    if (p.bf16 && forced >= 0 && !forced_has_bf16(f6 ? 6 : 8, forced)) return MIXQ_EINVAL;
+    return MIXQ_OK;
+}
+
+// Every fused entry point, fp16 and bf16 (include/mixq_hip.h, "bf16 layers"): validate, plan, launch what the plan says - one launch, or
+// two for an N split.
+int gemm_fused(const MixqFusedProblem& p, int K, int layout, int bit, mixq_stream_t stream)
+{
+    const int forced = g_forced_cfg.get();                       // this device's forced configuration (-1: automatic)
+    if (int rc = validate_fused(p, K, layout, bit, forced)) return rc;
+    if (p.M == 0 || p.N == 0) return MIXQ_OK;
+    const Route r = plan_route(bit, layout, p.M, p.N, p.KB, p.act, p.row_amax != nullptr, p.bf16, forced);
+    if (r.status) return r.status;
+    const hipStream_t st = mixq_stream(stream);
+    const bool wf16 = layout != MIXQ_XW_F6X128 && (layout & MIXQ_W_F16X64);
+    if (r.kind == ROUTE_SKINNY) return mixq_skinny_launch(p, bit, wf16 ? 1 : 0, st);
+    if (r.kind == ROUTE_SK) return mixq_sk_launch(p, r.cfg, bit, st);
+    if (r.kind == ROUTE_WR) {
+        const int wbit = layout == MIXQ_XW_F6X128 ? 6 : bit;
+        unsigned long long* trace = p.bf16 ? nullptr : g_trace;  // (first launch of a split only; the bf16 forms carry no stamps)
+        if (r.n1 <= 0) return mixq_wr_launch(p, r.cfg, wbit, trace, st, 0, p.N);
+        if (int rc = mixq_wr_launch(p, r.cfg, wbit, trace, st, 0, r.n1)) return rc;
+        return mixq_wr_launch(p, r.cfg2, wbit, nullptr, st, r.n1, p.N - r.n1);
+    }
+    GemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.qx = static_cast<const uint8_t*>(p.q_x); a.qw = static_cast<const uint8_t*>(p.q_w);
+    a.sx = p.x_scale; a.sw = p.scale_col; a.xo = p.x_out; a.wo = p.w_out; a.n_out_dev = p.n_out_dev; a.addend = p.addend; a.bias = p.bias; a.y = p.y;
+    a.M = p.M; a.N = p.N; a.KB = p.KB; a.ldxo = p.ldxo; a.ldwo = p.ldwo; a.n_out = p.n_out; a.lda = p.lda; a.ldy = p.ldy; a.act = p.act;
+    a.x_packed = (layout & MIXQ_X_PACKED) ? 1 : 0;
+    a.w_packed = ((layout & MIXQ_W_PACKED) || wf16) ? 1 : 0; a.w_f16 = wf16 ? 1 : 0;   // (a forced tiling on the fragment-order image: remapped DMA source)
+    a.xrows16 = (p.M + 15) & ~15; a.wrows16 = (p.N + 15) & ~15;
+    return launch_gemm(a, bit == 8 ? 0 : 1, st, r.cfg);
+}
+
+// ---- what the queries of the C ABI ask the planner ------------------------------------------------------------------------------------
+// the automatic route of a problem whose weights are in the packed format `fmt` (the activations are P16X64, or R6X128 beside F6X128
+// weights); status MIXQ_EINVAL for a format / bit combination no entry point takes.  (A format that is no weight format reads as P16X64.)
+Route query_route(int M, int N, int K, int bit, int fmt, bool bf16)
+{
+    if (fmt == MIXQ_FMT_F6X128 && bit != 4) return Route{MIXQ_EINVAL, ROUTE_LDS, -1, 0, -1};
+    const int layout = fmt == MIXQ_FMT_F6X128 ? MIXQ_XW_F6X128 : (fmt == MIXQ_FMT_PLAIN ? 0 : (MIXQ_X_PACKED | (fmt == MIXQ_FMT_F16X64 ? MIXQ_W_F16X64 : MIXQ_W_PACKED)));
+    return plan_route(bit, layout, M, N, bit == 8 ? K : K / 2, MIXQ_ACT_NONE, false, bf16, -1);
+}
+int pick_split(int M, int N, int K, int bit, int fmt, int* n1, int* cfg2, bool bf16)
+{
+    if ((bit != 8 && bit != 4) || M <= 0 || N <= 0 || K <= 0 || !n1 || !cfg2) return MIXQ_EINVAL;
+    const Route r = query_route(M, N, K, bit, fmt, bf16);
+    if (r.status || r.kind != ROUTE_WR || r.n1 <= 0) return 0;
+    *n1 = r.n1; *cfg2 = cfg_id(ROUTE_WR, r.cfg2);
+    return 1;
+}
+int amax_supported(int M, int N, int K, int layout, bool bf16)
+{
+    if (M <= 0 || N <= 0 || K <= 0 || (K % 64) || (N & 3) || layout != (MIXQ_X_PACKED | MIXQ_W_F16X64)) return 0;
+    return plan_route(8, layout, M, N, K, MIXQ_ACT_NONE, true, bf16, -1).status == MIXQ_OK ? 1 : 0;
 }
 
 }  // namespace
@@ -1036,16 +1064,16 @@ extern "C" int mixq_gemm_i8_fused_bf16(const int8_t* q_x, const int8_t* q_w, con
                                        const int32_t* n_out_dev, const uint16_t* addend, int lda, const uint16_t* bias,
                                        uint16_t* y, int ldy, int M, int N, int K, int act, int layout, mixq_stream_t stream)
 {
-    return gemm_fused_bf16(q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
-                           ldy, M, N, K, act, layout, 8, stream);
+    return gemm_fused({q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y, ldy, M, N, K, act,
+                       nullptr, nullptr, true}, K, layout, 8, stream);
 }
 extern "C" int mixq_gemm_i4_fused_bf16(const uint8_t* q_x, const uint8_t* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
                                        const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out,
                                        const int32_t* n_out_dev, const uint16_t* addend, int lda, const uint16_t* bias,
                                        uint16_t* y, int ldy, int M, int N, int K, int act, int layout, mixq_stream_t stream)
 {
-    return gemm_fused_bf16(q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
-                           ldy, M, N, K, act, layout, 4, stream);
+    return gemm_fused({q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y, ldy, M, N, K / 2, act,
+                       nullptr, nullptr, true}, K, layout, 4, stream);
 }
 // (row_amax then holds maxima of bf16 bit patterns: what mixq_quant_known_amax_bf16 reads)
 extern "C" int mixq_gemm_i8_fused_amax_bf16(const int8_t* q_x, const int8_t* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
@@ -1055,13 +1083,13 @@ extern "C" int mixq_gemm_i8_fused_amax_bf16(const int8_t* q_x, const int8_t* q_w
                                             const uint32_t* col_mask, mixq_stream_t stream)
 {
     if (!row_amax) return MIXQ_EINVAL;
-    return gemm_fused_bf16(q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
-                           ldy, M, N, K, act, layout, 8, stream, row_amax, col_mask);
+    return gemm_fused({q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y, ldy, M, N, K, act,
+                       row_amax, col_mask, true}, K, layout, 8, stream);
 }
 // (every batch size runs a weights-in-registers tiling in bf16: no small-batch exception)
 extern "C" int mixq_gemm_amax_supported_bf16(int M, int N, int K, int layout)
 {
-    return (M > 0 && N > 0 && K > 0 && (K % 64) == 0 && (N & 3) == 0 && layout == (MIXQ_X_PACKED | MIXQ_W_F16X64)) ? 1 : 0;
+    return amax_supported(M, N, K, layout, true);
 }
 
 extern "C" int mixq_gemm_i8_fused(const int8_t* q_x, const int8_t* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
@@ -1069,8 +1097,8 @@ extern "C" int mixq_gemm_i8_fused(const int8_t* q_x, const int8_t* q_w, const ui
                                   const int32_t* n_out_dev, const uint16_t* addend, int lda, const uint16_t* bias,
                                   uint16_t* y, int ldy, int M, int N, int K, int act, int layout, mixq_stream_t stream)
 {
-    return gemm_fused_common(q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
-                             ldy, M, N, K, act, layout, 8, stream);
+    return gemm_fused({q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y, ldy, M, N, K, act,
+                       nullptr, nullptr, false}, K, layout, 8, stream);
 }
 
 // The same GEMM that also leaves, for the quantiser of the NEXT layer, the per-row maximum of |y| over the columns that layer does not
@@ -1083,16 +1111,13 @@ extern "C" int mixq_gemm_i8_fused_amax(const int8_t* q_x, const int8_t* q_w, con
 {
     if (!row_amax) return MIXQ_EINVAL;
     if (!(layout & MIXQ_W_F16X64)) return MIXQ_ESHAPE;
-    return gemm_fused_common(q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
-                             ldy, M, N, K, act, layout, 8, stream, row_amax, col_mask);
+    return gemm_fused({q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y, ldy, M, N, K, act,
+                       row_amax, col_mask, false}, K, layout, 8, stream);
 }
 // 1 when mixq_gemm_i8_fused_amax serves (M, N, K) with this layout, else 0 (the caller then quantises the next layer the usual way)
 extern "C" int mixq_gemm_amax_supported(int M, int N, int K, int layout)
 {
-    if (M <= 0 || N <= 0 || K <= 0 || (K % 64) || !(layout & MIXQ_W_F16X64) || !(layout & MIXQ_X_PACKED)) return 0;
-    const bool wide_wr = N >= 8192;
-    if (!wide_wr && mixq_skinny_applies(8, M, N, K, true, true)) return 0;
-    return 1;
+    return amax_supported(M, N, K, layout, false);
 }
 
 extern "C" int mixq_gemm_i4_fused(const uint8_t* q_x, const uint8_t* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
@@ -1100,8 +1125,8 @@ extern "C" int mixq_gemm_i4_fused(const uint8_t* q_x, const uint8_t* q_w, const 
                                   const int32_t* n_out_dev, const uint16_t* addend, int lda, const uint16_t* bias,
                                   uint16_t* y, int ldy, int M, int N, int K, int act, int layout, mixq_stream_t stream)
 {
-    return gemm_fused_common(q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y,
-                             ldy, M, N, K, act, layout, 4, stream);
+    return gemm_fused({q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y, ldy, M, N, K / 2, act,
+                       nullptr, nullptr, false}, K, layout, 4, stream);
 }
 
 extern "C" int mixq_gemm_i8(const int8_t* q_x, const int8_t* q_w, int32_t* y32, int ldy, int M, int N, int K,
@@ -1116,7 +1141,7 @@ extern "C" int mixq_gemm_i8(const int8_t* q_x, const int8_t* q_w, int32_t* y32, 
     a.qx = reinterpret_cast<const uint8_t*>(q_x); a.qw = reinterpret_cast<const uint8_t*>(q_w);
     a.y32 = y32; a.M = M; a.N = N; a.KB = K; a.ldy = ldy;
     a.xrows16 = (M + 15) & ~15; a.wrows16 = (N + 15) & ~15;
-    return launch_gemm(a, 2, mixq_stream(stream));
+    return launch_gemm(a, 2, mixq_stream(stream), lds_config(g_forced_cfg.get(), M, N));
 }
 
 extern "C" int mixq_dequant(const int32_t* y32, int ldy32, const uint16_t* x_scale, const uint16_t* scale_col,
@@ -1139,10 +1164,6 @@ extern "C" int mixq_dequant(const int32_t* y32, int ldy32, const uint16_t* x_sca
                                 lda, bias, y, ldy, M, N, act);
     return mixq_launch_status();
 }
-
-// Config ids: [0, NUM_CFGS) data-parallel tilings of this file, then the stream-K forms, "decode32", then the
-// weights-in-registers tilings of gemm_wreg.hip (MIXQ_FMT_F16X64 operands only).
-static int total_configs() { return NUM_CFGS + mixq_sk_num_configs() + 1 + mixq_wr_num_configs(); }
 
 // ---- per-device registry: the hand-off workspace (stream-K / pairwise split-K: tuning build) and the CU count -------------------------
 namespace {
@@ -1194,54 +1215,28 @@ extern "C" int mixq_gemm_set_krot(int v) { return mixq_wr_set_krot(v); }
 extern "C" int mixq_gemm_num_configs(void) { return total_configs(); }
 extern "C" int mixq_gemm_config_name(int cfg, char* buf, int cap) {
     if (cfg < 0 || cfg >= total_configs() || !buf || cap <= 0) return MIXQ_EINVAL;
-    const int sk0 = NUM_CFGS, dec = sk0 + mixq_sk_num_configs(), wr0 = dec + 1;
-    snprintf(buf, cap, "%s", cfg < sk0 ? g_cfgs[cfg].name : (cfg < dec ? mixq_sk_config_name(cfg - sk0)
-                                                                      : (cfg == dec ? "decode32" : mixq_wr_config_name(cfg - wr0))));
+    int c = -1;
+    const RouteKind kind = cfg_family(cfg, &c);
+    snprintf(buf, cap, "%s", kind == ROUTE_LDS ? g_cfgs[c].name : (kind == ROUTE_SK ? mixq_sk_config_name(c)
+                                                                   : (kind == ROUTE_SKINNY ? "decode32" : mixq_wr_config_name(c))));
     return MIXQ_OK;
 }
 extern "C" int mixq_gemm_pick_config(int M, int N, int K, int bit) {
     if (M <= 0 || N <= 0 || K <= 0 || (bit != 4 && bit != 8)) return MIXQ_EINVAL;
-    const int KB = bit == 8 ? K : K / 2;
-    const int sk = pick_stream_k(M, N, KB);
-    if (sk >= 0 && mixq_sk_usable(sk)) return NUM_CFGS + sk;
-    return pick_config(M, N, KB, true);
+    const int sk = pick_stream_k(M, N, bit == 8 ? K : K / 2);
+    if (sk >= 0 && mixq_sk_usable(sk)) return cfg_id(ROUTE_SK, sk);
+    return pick_config(M, N);
 }
-// The config the automatic choice runs for weights in the packed format `fmt` (MIXQ_FMT_P16X64 / MIXQ_FMT_F16X64; the
-// activations are P16X64 either way).
-extern "C" int mixq_gemm_pick_split(int M, int N, int K, int bit, int fmt, int* n1, int* cfg2) {
-    if ((bit != 8 && bit != 4) || M <= 0 || N <= 0 || K <= 0 || !n1 || !cfg2) return MIXQ_EINVAL;
-    const bool f6 = fmt == MIXQ_FMT_F6X128 && bit == 4;
-    if (!f6 && !(fmt == MIXQ_FMT_F16X64 && bit == 8)) return 0;
-    const int KB = bit == 8 ? K : K / 2, wbit = f6 ? 6 : 8;
-    if (!f6 && ((N < 8192 && mixq_skinny_applies(8, M, N, KB, true, true)) || mixq_wr_ksplit_pays(M, N, KB))) return 0;
-    int c2 = -1;
-    if (!mixq_wr_split(wbit, M, N, KB, mixq_wr_pick(wbit, M, N, KB), n1, &c2)) return 0;
-    *cfg2 = NUM_CFGS + mixq_sk_num_configs() + 1 + c2;
-    return 1;
-}
-// ... of the bf16 entry points: gemm_fused_bf16's own decision (its pick among the tilings with a bf16 form, no small-batch or long-K exception,
-// and a second tiling that has a bf16 form too)
-extern "C" int mixq_gemm_pick_split_bf16(int M, int N, int K, int bit, int fmt, int* n1, int* cfg2) {
-    if ((bit != 8 && bit != 4) || M <= 0 || N <= 0 || K <= 0 || !n1 || !cfg2) return MIXQ_EINVAL;
-    const bool f6 = fmt == MIXQ_FMT_F6X128 && bit == 4;
-    if (!f6 && !(fmt == MIXQ_FMT_F16X64 && bit == 8)) return 0;
-    const int KB = bit == 8 ? K : K / 2, wbit = f6 ? 6 : 8;
-    const int c = mixq_wr_pick_bf16(wbit, M, N, KB);
-    int c2 = -1;
-    if (c < 0 || !mixq_wr_split(wbit, M, N, KB, c, n1, &c2) || !mixq_wr_has_bf16(wbit, c2)) return 0;
-    *cfg2 = NUM_CFGS + mixq_sk_num_configs() + 1 + c2;
-    return 1;
-}
+// The automatic choice for weights in the packed format `fmt` (include/mixq_hip.h), read from the planner that the launches follow
+// (plan_route with no forced configuration): the config id, and whether the launch is an N split (then *n1 weight rows run the picked
+// tiling and the rest tiling *cfg2).  The _bf16 form answers for the `_bf16` entry points, which pick among the tilings with a bf16 form.
 extern "C" int mixq_gemm_pick_config_fmt(int M, int N, int K, int bit, int fmt) {
     if (M <= 0 || N <= 0 || K <= 0 || (bit != 4 && bit != 8)) return MIXQ_EINVAL;
-    const int KB = bit == 8 ? K : K / 2;
-    const int dec = NUM_CFGS + mixq_sk_num_configs();
-    if (fmt == MIXQ_FMT_F6X128) return bit == 4 ? dec + 1 + mixq_wr_pick(6, M, N, KB) : MIXQ_EINVAL;   // (FP6-coded operands: the weights-in-registers kernels only)
-    const bool wide_wr = fmt == MIXQ_FMT_F16X64 && bit == 8 && N >= 8192;                 // as in gemm_fused_common
-    if (!wide_wr && fmt != MIXQ_FMT_PLAIN && mixq_skinny_applies(bit, M, N, KB, true, true)) return dec;
-    if (fmt == MIXQ_FMT_F16X64) return dec + 1 + ((bit == 8 && mixq_wr_ksplit_pays(M, N, KB)) ? mixq_wr_ksplit_config() : mixq_wr_pick(bit, M, N, KB));
-    return mixq_gemm_pick_config(M, N, K, bit);
+    const Route r = query_route(M, N, K, bit, fmt, false);
+    return r.status ? r.status : cfg_id(r.kind, r.cfg);
 }
+extern "C" int mixq_gemm_pick_split(int M, int N, int K, int bit, int fmt, int* n1, int* cfg2) { return pick_split(M, N, K, bit, fmt, n1, cfg2, false); }
+extern "C" int mixq_gemm_pick_split_bf16(int M, int N, int K, int bit, int fmt, int* n1, int* cfg2) { return pick_split(M, N, K, bit, fmt, n1, cfg2, true); }
 
 extern "C" int mixq_version(void) { return 1002; }   // 1.1: the _bf16 quantise entry points; 1.2: the _bf16 GEMMs and mixq_linear_forward_bf16
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "common.h"
 
 // per-device state (one process may drive several GPUs), gemm.hip: the workspace registered with mixq_gemm_set_workspace and the CU count
 struct MixqDevState { void* ws; size_t bytes; int num_cu; };
@@ -22,15 +23,11 @@ const char* mixq_sk_config_name(int c);
 size_t mixq_sk_workspace_need(int c, int G);
 bool mixq_sk_usable(int c);                  // workspace registered and large enough for config c on this device
 long long mixq_sk_workspace_bytes();
-int mixq_sk_launch(int c, int bit, const void* q_x, const void* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
-                   const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
-                   const uint16_t* addend, int lda, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int KB, int act,
-                   hipStream_t st);
+int mixq_sk_launch(const MixqFusedProblem& p, int c, int bit, hipStream_t st);
 #else                                        // the product library holds no stream-K kernel: the dispatcher's questions answer themselves
 inline int mixq_sk_num_configs() { return 0; }
 inline const char* mixq_sk_config_name(int) { return ""; }
 inline bool mixq_sk_usable(int) { return false; }
 inline long long mixq_sk_workspace_bytes() { return 0; }
-inline int mixq_sk_launch(int, int, const void*, const void*, const uint16_t*, const uint16_t*, const uint16_t*, int, const uint16_t*, int, int,
-                          const int32_t*, const uint16_t*, int, const uint16_t*, uint16_t*, int, int, int, int, int, hipStream_t) { return -1; }
+inline int mixq_sk_launch(const MixqFusedProblem&, int, int, hipStream_t) { return -1; }
 #endif

@@ -457,18 +457,16 @@ bool mixq_sk_usable(int c) {
     return cus > 0 && mixq_sk_workspace_need(c, cus) <= d->bytes;
 }
 
-int mixq_sk_launch(int c, int bit, const void* q_x, const void* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
-                   const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
-                   const uint16_t* addend, int lda, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int KB, int act,
-                   hipStream_t st)
+int mixq_sk_launch(const MixqFusedProblem& p, int c, int bit, hipStream_t st)
 {
     if (!mixq_sk_usable(c)) return MIXQ_EINVAL;
+    const int M = p.M, N = p.N, KB = p.KB;
     const SkConfig& g = g_sk[c];
     SkArgs a;
     memset(&a, 0, sizeof(a));
-    a.qx = static_cast<const uint8_t*>(q_x); a.qw = static_cast<const uint8_t*>(q_w);
-    a.sx = x_scale; a.sw = scale_col; a.xo = x_out; a.wo = w_out; a.n_out_dev = n_out_dev; a.addend = addend; a.bias = bias; a.y = y;
-    a.M = M; a.N = N; a.KB = KB; a.ldxo = ldxo; a.ldwo = ldwo; a.n_out = n_out; a.lda = lda; a.ldy = ldy; a.act = act;
+    a.qx = static_cast<const uint8_t*>(p.q_x); a.qw = static_cast<const uint8_t*>(p.q_w);
+    a.sx = p.x_scale; a.sw = p.scale_col; a.xo = p.x_out; a.wo = p.w_out; a.n_out_dev = p.n_out_dev; a.addend = p.addend; a.bias = p.bias; a.y = p.y;
+    a.M = M; a.N = N; a.KB = KB; a.ldxo = p.ldxo; a.ldwo = p.ldwo; a.n_out = p.n_out; a.lda = p.lda; a.ldy = p.ldy; a.act = p.act;
     a.tiles_m = (M + g.bm - 1) / g.bm; a.tiles_n = (N + g.bn - 1) / g.bn;
     a.xrows16 = (M + 15) & ~15; a.wrows16 = (N + 15) & ~15;
     a.nk = KB / BKB;

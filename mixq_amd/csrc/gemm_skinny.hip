@@ -222,14 +222,13 @@ bool mixq_skinny_applies(int bit, int M, int N, int KB, bool x_packed, bool w_pa
     return (bit == 8 || bit == 4) && M >= 1 && M <= 32 && x_packed && w_packed && (KB % 64) == 0 && N >= 4;
 }
 
-int mixq_skinny_launch(int bit, const void* q_x, const void* q_w, const uint16_t* x_scale, const uint16_t* scale_col, const uint16_t* x_out,
-                       int ldxo, const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev, const uint16_t* addend,
-                       int lda, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int KB, int act, int wf16, hipStream_t st)
+int mixq_skinny_launch(const MixqFusedProblem& p, int bit, int wf16, hipStream_t st)
 {
+    const int M = p.M, N = p.N;
     SkinnyArgs a;
-    a.qx = static_cast<const uint8_t*>(q_x); a.qw = static_cast<const uint8_t*>(q_w);
-    a.sx = x_scale; a.sw = scale_col; a.xo = x_out; a.wo = w_out; a.n_out_dev = n_out_dev; a.addend = addend; a.bias = bias; a.y = y;
-    a.M = M; a.N = N; a.KB = KB; a.ldxo = ldxo; a.ldwo = ldwo; a.n_out = n_out; a.lda = lda; a.ldy = ldy; a.act = act;
+    a.qx = static_cast<const uint8_t*>(p.q_x); a.qw = static_cast<const uint8_t*>(p.q_w);
+    a.sx = p.x_scale; a.sw = p.scale_col; a.xo = p.x_out; a.wo = p.w_out; a.n_out_dev = p.n_out_dev; a.addend = p.addend; a.bias = p.bias; a.y = p.y;
+    a.M = M; a.N = N; a.KB = p.KB; a.ldxo = p.ldxo; a.ldwo = p.ldwo; a.n_out = p.n_out; a.lda = p.lda; a.ldy = p.ldy; a.act = p.act;
     a.xrows16 = (M + 15) & ~15; a.wrows16 = (N + 15) & ~15; a.wf16 = wf16;
     if (bit == 8) hipLaunchKernelGGL((gemm_skinny_kernel<4, 2, false>), dim3((N + 31) / 32), dim3(SKW * 64), 0, st, a);
     else          hipLaunchKernelGGL((gemm_skinny_kernel<4, 2, true>), dim3((N + 31) / 32), dim3(SKW * 64), 0, st, a);

@@ -2,18 +2,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "common.h"
 
 int mixq_wr_num_configs();
 int mixq_wr_set_krot(int v);                 // k-step rotation between neighbouring N tiles (tuning; results do not depend on it)
 const char* mixq_wr_config_name(int c);
 // config for (M, N, KB) or -1 when the data-parallel kernels of gemm.hip should run instead
 int mixq_wr_pick(int bit, int M, int N, int KB);
-int mixq_wr_launch(int c, int bit, const void* q_x, const void* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
-                   const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
-                   const uint16_t* addend, int lda, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int KB, int act,
-                   unsigned long long* trace, hipStream_t st, uint32_t* row_amax = nullptr, const uint32_t* amax_mask = nullptr,
-                   int n_begin = 0, int n_cols = -1,      // the launch covers the weight rows [n_begin, n_begin + n_cols) (default: all from n_begin)
-                   bool bf16 = false);                    // x_out, w_out, addend and y are bfloat16 (bit 8 or 6; a tiling without a bf16 form: MIXQ_EINVAL)
+// one launch of tiling c over the weight rows [n_begin, n_begin + n_cols) of problem p (only the launch that ends at p.N may hold a partial
+// tile); bit: 8, 4, or 6 (int4 as FP6 codes).  p.bf16 with a tiling without a bf16 form: MIXQ_EINVAL
+int mixq_wr_launch(const MixqFusedProblem& p, int c, int bit, unsigned long long* trace, hipStream_t st, int n_begin, int n_cols);
 // the bf16 forms: the tiling for a problem (-1: none), and whether a (forced) configuration has one
 int mixq_wr_pick_bf16(int bit, int M, int N, int KB);   // bit: 8, or 6 (int4 as FP6 codes)
 bool mixq_wr_has_bf16(int bit, int c);

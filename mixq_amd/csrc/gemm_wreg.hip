@@ -1934,24 +1934,21 @@ bool mixq_wr_split(int bit, int M, int N, int KB, int c, int* n1, int* c2)
 
 
 // bit: 8, 4 (nibble-packed operands) or 6 (int4 as FP6 codes, MIXQ_FMT_F6X128 operands; KB is K / 2 as for bit 4)
-int mixq_wr_launch(int c, int bit, const void* q_x, const void* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
-                   const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
-                   const uint16_t* addend, int lda, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int KB, int act,
-                   unsigned long long* trace, hipStream_t st, uint32_t* row_amax, const uint32_t* amax_mask, int n_begin, int n_cols, bool bf16)
+int mixq_wr_launch(const MixqFusedProblem& p, int c, int bit, unsigned long long* trace, hipStream_t st, int n_begin, int n_cols)
 {
+    const int M = p.M, N = p.N, KB = p.KB;
     if (c < 0 || c >= NUM_WR) return MIXQ_EINVAL;
-    if (bf16 && (act == MIXQ_ACT_SILU_PAIR || !mixq_wr_bf16_kernel(bit, c))) return MIXQ_EINVAL;    // (no paired epilogue, no form outside gemm_wreg_bf16.hip's table)
-    if (n_cols < 0) n_cols = N - n_begin;                                   // (the default: every weight row from n_begin on)
+    if (p.bf16 && (p.act == MIXQ_ACT_SILU_PAIR || !mixq_wr_bf16_kernel(bit, c))) return MIXQ_EINVAL;    // (no paired epilogue, no form outside gemm_wreg_bf16.hip's table)
     if (n_begin < 0 || (n_begin & 63) || n_cols <= 0 || n_begin + n_cols > N) return MIXQ_EINVAL;
-    const bool pair = act == MIXQ_ACT_SILU_PAIR;                            // (the paired epilogue is a kernel form, not a run-time switch)
-    if (pair && ((bit != 8 && bit != 6) || (N & 3) || addend)) return MIXQ_EINVAL;
+    const bool pair = p.act == MIXQ_ACT_SILU_PAIR;                          // (the paired epilogue is a kernel form, not a run-time switch)
+    if (pair && ((bit != 8 && bit != 6) || (N & 3) || p.addend)) return MIXQ_EINVAL;
     const WrConfig& g = g_wr[c];
     WrArgs a;
     memset(&a, 0, sizeof(a));
-    a.qx = static_cast<const uint8_t*>(q_x); a.qw = static_cast<const uint8_t*>(q_w);
-    a.sx = x_scale; a.sw = scale_col; a.xo = x_out; a.wo = w_out; a.n_out_dev = n_out_dev;
-    a.addend = addend; a.bias = bias; a.y = y;
-    a.M = M; a.N = N; a.KB = KB; a.ldxo = ldxo; a.ldwo = ldwo; a.n_out = n_out; a.lda = lda; a.ldy = ldy; a.act = act;
+    a.qx = static_cast<const uint8_t*>(p.q_x); a.qw = static_cast<const uint8_t*>(p.q_w);
+    a.sx = p.x_scale; a.sw = p.scale_col; a.xo = p.x_out; a.wo = p.w_out; a.n_out_dev = p.n_out_dev;
+    a.addend = p.addend; a.bias = p.bias; a.y = p.y;
+    a.M = M; a.N = N; a.KB = KB; a.ldxo = p.ldxo; a.ldwo = p.ldwo; a.n_out = p.n_out; a.lda = p.lda; a.ldy = p.ldy; a.act = p.act;
     const int bm = g.mb * 16, bn = g.wnb * 64;
     a.tiles_m = cdiv(M, bm); a.tiles_n = cdiv(n_cols, bn); a.n_begin = n_begin;
     if (n_begin + n_cols < N && n_cols % bn) return MIXQ_EINVAL;           // (only the launch that ends at N may hold a partial tile)
@@ -1968,9 +1965,9 @@ int mixq_wr_launch(int c, int bit, const void* q_x, const void* q_w, const uint1
         if (static_cast<long long>(a.tiles_m) * a.tiles_n * (a.gm * static_cast<long long>(a.tiles_n)) >= (1ll << 32)) return MIXQ_ESHAPE;   // (exactness bound of the reciprocals)
     }
     a.trace = trace;
-    a.row_amax = row_amax; a.amax_mask = amax_mask;
+    a.row_amax = p.row_amax; a.amax_mask = p.amax_mask;
     void (*k)(const WrArgs) = pair ? (bit == 8 ? g.k8p : g.k6p) : (bit == 8 ? g.k8 : (bit == 6 ? g.k6 : g.k4));
-    const void* kh = bf16 ? mixq_wr_bf16_kernel(bit, c) : reinterpret_cast<const void*>(k);     // (the bf16 forms live in gemm_wreg_bf16.hip's code object)
+    const void* kh = p.bf16 ? mixq_wr_bf16_kernel(bit, c) : reinterpret_cast<const void*>(k);     // (the bf16 forms live in gemm_wreg_bf16.hip's code object)
     if (!kh) return MIXQ_EINVAL;
     int units = a.tiles_m * a.tiles_n;
     if (c == WR_KSPLIT) {
@@ -1985,7 +1982,7 @@ int mixq_wr_launch(int c, int bit, const void* q_x, const void* q_w, const uint1
     const size_t ring = (bit == 6 ? static_cast<size_t>(g.nstage6) * g.mb * 1536 + 4 * g.mb * 1024 : static_cast<size_t>(g.nstage + 2) * g.mb * 1024) + 64 /* panel flags */ + static_cast<size_t>(bm) * 4 + static_cast<size_t>(bn) * 8 /* scales */, stg = ((static_cast<size_t>(bm) * (bn * 2 + 16) + 15) & ~static_cast<size_t>(15)) + 16 * bm * 4;   // ring + the tail's X_out blocks | staging tile + row-maximum slots
     const size_t shm = ring > stg ? ring : stg;
     if (int rc = mixq_ensure_dynamic_lds(kh, shm)) return rc;
-    if (bf16) {
+    if (p.bf16) {
         void* params[] = {&a};
         if (hipError_t e = hipLaunchKernel(kh, dim3(units), dim3((WR_CW + g.loaders) * 64), params, shm, st)) return static_cast<int>(e);
     } else {

@@ -77,6 +77,12 @@ def test_bf16_gemms_answer_bad_arguments_and_unserved_layouts_before_any_launch(
     assert lib.mixq_gemm_i4_fused_bf16(*_gemm_args(fake, wf16)) == ESHAPE
     assert lib.mixq_gemm_i8_fused_bf16(*_gemm_args(fake, wf16, act=_capi.ACT_SILU_PAIR)) == ESHAPE
     assert lib.mixq_gemm_i8_fused_bf16(*_gemm_args(fake, wf16, K=96)) == ESHAPE                           # K % 64
+    # coincident faults, the earlier check answers: the paired act is refused before the layout is looked at (and before its addend, which fp16
+    # calls a bad argument); the missing multiplier before a bad K
+    for layout in (0, _capi.X_PACKED | _capi.W_PACKED, wf16):
+        assert lib.mixq_gemm_i8_fused_bf16(*_gemm_args(fake, layout, act=_capi.ACT_SILU_PAIR, addend=fake)) == ESHAPE
+    assert lib.mixq_gemm_i8_fused(*_gemm_args(fake, wf16, act=_capi.ACT_SILU_PAIR, addend=fake)) == EINVAL
+    assert lib.mixq_gemm_i8_fused_bf16(*_gemm_args(fake, wf16, K=96, act=_capi.ACT_SILU_MUL)) == EINVAL
     assert lib.mixq_gemm_amax_supported_bf16(8, 64, 128, wf16) == 1                                      # every batch size, small ones included
     assert lib.mixq_gemm_amax_supported_bf16(64, 64, 96, wf16) == 0
     # the one-call forward: NULL block, and a weight layout the bf16 GEMMs do not read - said before the quantise pass is launched
@@ -102,6 +108,10 @@ def test_a_forced_tiling_without_a_bf16_form_answers_einval():
                 assert lib.mixq_gemm_i8_fused_bf16(*_gemm_args(fake, wf16)) == _capi.MIXQ_EINVAL, name
             if name not in BF16_FP6:
                 assert lib.mixq_gemm_i4_fused_bf16(*_gemm_args(fake, f6)) == _capi.MIXQ_EINVAL, name
+            if name not in BF16_INT8:                           # ... ahead of the M == 0 early-out, where fp16 answers MIXQ_OK
+                empty = list(_gemm_args(fake, wf16))
+                empty[15] = 0
+                assert lib.mixq_gemm_i8_fused_bf16(*empty) == _capi.MIXQ_EINVAL and lib.mixq_gemm_i8_fused(*empty) == 0, name
     finally:
         assert lib.mixq_gemm_set_config(-1) == 0
 

@@ -122,6 +122,32 @@ def test_argument_validation_without_device():
     for fn in (lib.mixq_gemm_i8_fused_amax, lib.mixq_gemm_i8_fused_amax_bf16):
         amax = lambda y, addend: fn(one, one, one, one, None, 0, None, 0, 0, None, addend, 64, None, y, 64, 0, 64, 128, 0, wf16, one, None, None)
         assert amax(one, None) == 0 and amax(p4, None) == _capi.MIXQ_EINVAL and amax(one, p4) == _capi.MIXQ_EINVAL
+    # coincident faults: the order of the checks is part of the behaviour, the earlier one answers (fp16 and bf16 differ where their kernels do)
+    EINVAL, ESHAPE = _capi.MIXQ_EINVAL, _capi.MIXQ_ESHAPE
+    i8, i8bf, i4, i4bf = lib.mixq_gemm_i8_fused, lib.mixq_gemm_i8_fused_bf16, lib.mixq_gemm_i4_fused, lib.mixq_gemm_i4_fused_bf16
+
+    def call(fn, layout, M=4, act=0, addend=None, ldy=64):
+        return fn(one, one, one, one, None, 0, None, 0, 0, None, addend, 64, None, one, ldy, M, 64, 128, act, layout, None)
+    for fn, layout in ((i8, 0), (i8, wf16), (i4, _capi.XW_F6X128), (i8bf, wf16), (i4bf, _capi.XW_F6X128)):
+        assert call(fn, layout, act=_capi.ACT_SILU_MUL, ldy=62) == EINVAL          # no multiplier (EINVAL) and a bad ldy (ESHAPE)
+        assert call(fn, layout, act=_capi.ACT_SILU_MUL, ldy=62, M=0) == EINVAL
+    assert call(i8, wf16, act=_capi.ACT_SILU_PAIR, addend=one) == EINVAL           # the paired form takes no addend ...
+    assert call(i8bf, wf16, act=_capi.ACT_SILU_PAIR, addend=one) == ESHAPE         # ... and does not exist in bf16: said first there
+    assert call(i8bf, _capi.X_PACKED | _capi.W_PACKED, act=_capi.ACT_SILU_PAIR) == ESHAPE      # (paired act AND a layout bf16 does not serve)
+    assert call(i8bf, 64, act=_capi.ACT_SILU_PAIR) == EINVAL                       # (an unknown layout bit is answered before the act)
+    both_w = _capi.X_PACKED | _capi.W_PACKED | _capi.W_F16X64
+    assert call(i8, both_w) == EINVAL and call(i8bf, both_w) == ESHAPE             # two weight formats at once: fp16 a bad argument, bf16 an unserved layout
+    assert call(i8, _capi.W_F16X64) == EINVAL and call(i8bf, _capi.W_F16X64) == ESHAPE
+    # a forced tiling without a bf16 form (config 0: an LDS-staged tiling) and an empty problem: bf16 refuses the configuration before the
+    # M == 0 early-out, fp16 - whose forced-configuration answers belong to the route - returns MIXQ_OK for the empty problem
+    try:
+        assert lib.mixq_gemm_set_config(0) == 0
+        assert call(i8bf, wf16, M=0) == EINVAL and call(i4bf, _capi.XW_F6X128, M=0) == EINVAL
+        assert call(i8, wf16, M=0) == 0 and call(i4, _capi.XW_F6X128, M=0) == 0
+        assert call(i4, _capi.XW_F6X128, M=4) == EINVAL                            # (FP6 codes: only the weights-in-registers kernels read them)
+        assert call(i8bf, wf16, M=0, ldy=62) == ESHAPE                             # (the shape checks still come first)
+    finally:
+        assert lib.mixq_gemm_set_config(-1) == 0
     dq = lambda y32=one, addend=None, bias=None, y=one, M=0: lib.mixq_dequant(y32, 64, one, one, addend, 64, bias, y, 64, M, 64, 0, None)
     assert dq() == 0 and dq(y=p8, addend=p8, y32=p4) == 0
     for M in (0, 4):
