@@ -38,7 +38,7 @@
  *     bias, x_scale, scale_col                           2 bytes, the natural alignment of an fp16 array: they are read in groups of four
  *                                                        through a vector type declared 2-byte aligned
  *     mixq_gemm_i8: y32                                  16-byte aligned (four int32 leave as one store); mixq_dequant reads y32 at 4 bytes
- *   mixq_gemm_w8a16 states its own (x 16 bytes, y 8 bytes).
+ *   mixq_gemm_w8a16 states its own (x 16 bytes, y 8 bytes; the addend of mixq_gemm_w8a16_addend 8 bytes, lda >= N - no broadcast row).
  */
 #ifndef MIXQ_HIP_H
 #define MIXQ_HIP_H
@@ -387,10 +387,23 @@ int mixq_rmsnorm_quant_fused_masked(const uint16_t* x, const uint16_t* weight, u
  * matrix (modules/linear.py:70-71; EETQ's *unprocessed* quantised tensor) into round16(N) * K bytes of offset-binary
  * (q + 128) MIXQ_FMT_F16X64 (rows = output channels) once per layer: the image the kernel's lanes load straight into their
  * MFMA operand registers.
- *   K % 64 == 0, N % 4 == 0, ldx % 8 == 0, x 16-byte aligned, ldy % 4 == 0, y 8-byte aligned. */
+ *   K % 64 == 0, N % 4 == 0, ldx % 8 == 0, x 16-byte aligned, ldy % 4 == 0, y 8-byte aligned.
+ *
+ * mixq_gemm_w8a16_addend (ABI 1.3) is the same GEMM with an addend in its epilogue - the residual stream of a decoder layer whose
+ * down_proj / fc_out is weight-only, added before the output is rounded instead of by a pass of its own:
+ *   y[m,n] = fp16( float(acc[m,n]) * float(scale_col[n]) + float(addend[m,n]) + float(bias[n]) )
+ * fp32 throughout, in this order (the addend in front of the bias, as in the fused GEMMs' act(z) + bias), ONE round-to-nearest-even
+ * to fp16 at the end; nothing saturates (65520 becomes inf).
+ *   addend  fp16 [M,lda] or NULL (then exactly mixq_gemm_w8a16, which forwards here).  lda >= N, lda % 4 == 0 (MIXQ_ESHAPE otherwise),
+ *           base 8-byte aligned (MIXQ_EINVAL otherwise): it moves as 8-byte pieces, like y - the alignment contract of the fused GEMMs'
+ *           addend.  Both are answered before any launch, in the order of the checks above (sizes and NULL operands, then strides,
+ *           then pointers); M == 0 runs every check and launches nothing.  Only rows < M and columns < N of the addend are read.
+ *           The addend must NOT alias y: a workgroup writes its tile of y while others may still read theirs of the addend. */
 int mixq_pack_w8a16(const int8_t* q_weight_kn, uint8_t* packed, int K, int N, mixq_stream_t stream);
 int mixq_gemm_w8a16(const uint16_t* x, int ldx, const uint8_t* w_packed, const uint16_t* scale_col, const uint16_t* bias,
                     uint16_t* y, int ldy, int M, int N, int K, mixq_stream_t stream);
+int mixq_gemm_w8a16_addend(const uint16_t* x, int ldx, const uint8_t* w_packed, const uint16_t* scale_col, const uint16_t* addend, int lda,
+                           const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int K, mixq_stream_t stream);
 int mixq_gemm_w8a16_set_config(int cfg);             /* tuning: force a tile config, -1 = automatic */
 int mixq_gemm_w8a16_num_configs(void);
 int mixq_gemm_w8a16_config_name(int cfg, char* buf, int cap);

@@ -88,6 +88,7 @@ SIGNATURES = {
     "mixq_rmsnorm_quant_fused_masked": [_P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _F, _I, _P],
     "mixq_pack_w8a16": [_P, _P, _I, _I, _P],
     "mixq_gemm_w8a16": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "mixq_gemm_w8a16_addend": [_P, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P],
     "mixq_gemm_w8a16_set_config": [_I],
     "mixq_gemm_w8a16_num_configs": [],
     "mixq_gemm_w8a16_config_name": [_I, C.c_char_p, _I],

@@ -1238,7 +1238,7 @@ extern "C" int mixq_gemm_pick_config_fmt(int M, int N, int K, int bit, int fmt) 
 extern "C" int mixq_gemm_pick_split(int M, int N, int K, int bit, int fmt, int* n1, int* cfg2) { return pick_split(M, N, K, bit, fmt, n1, cfg2, false); }
 extern "C" int mixq_gemm_pick_split_bf16(int M, int N, int K, int bit, int fmt, int* n1, int* cfg2) { return pick_split(M, N, K, bit, fmt, n1, cfg2, true); }
 
-extern "C" int mixq_version(void) { return 1002; }   // 1.1: the _bf16 quantise entry points; 1.2: the _bf16 GEMMs and mixq_linear_forward_bf16
+extern "C" int mixq_version(void) { return 1003; }   // 1.1: the _bf16 quantise entry points; 1.2: the _bf16 GEMMs and mixq_linear_forward_bf16; 1.3: mixq_gemm_w8a16_addend
 
 extern "C" int mixq_device_info(char* buf, int cap) {
     if (!buf || cap <= 0) return MIXQ_EINVAL;

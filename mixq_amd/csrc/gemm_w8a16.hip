@@ -1,4 +1,4 @@
-// Weight-only W8A16 Linear for gfx950:  Y[M,N] = X[M,K] (fp16) * (Wq[K,N] (int8) * scale_col[N]) + bias
+// Weight-only W8A16 Linear for gfx950:  Y[M,N] = X[M,K] (fp16) * (Wq[K,N] (int8) * scale_col[N]) (+ addend[M,N]) + bias
 // -- what the reference reaches through EETQ's `w8_a16_gemm(x, q_weight, scale_col)` (modules/linear.py:178-184; GPT-J
 // fc_out and the "down_weight_only" variants, utils/module.py:4-12).  EETQ is a third-party CUDA extension that is not
 // part of the reference tree and is not version-pinned; its CUTLASS-interleaved weight image is an implementation
@@ -32,7 +32,8 @@ namespace {
 struct WoArgs {
     const uint16_t* x; const uint8_t* w; const uint16_t* sw; const uint16_t* bias; uint16_t* y;
     int M, N, K, ldx, ldy, tiles_m, tiles_n, wblocks;
-};
+    const uint16_t* add; int lda;                         // optional addend [M, lda] (behind the fields the k loop reads: the preloaded
+};                                                        // kernel-argument dwords stay what they were)
 
 constexpr int WO_CW = 4;                              // consumer waves, 1 x 4 along N
 
@@ -63,7 +64,10 @@ __device__ __forceinline__ void cvt_u8x4(uint32_t d, uint32_t& o0, uint32_t& o1)
 // MB: 16-row token blocks per tile (BM = 16 MB), WNB: 16-channel weight blocks per wave (BN = 64 WNB), NSTAGE: X ring depth,
 // D: weight register ring depth (k-steps), LOADERS: DMA waves.  ABL (tuning only): 0 normal, 1 no weight loads, 2 no X traffic,
 // 3 MFMA only, 4 MFMA + conversions (results of 1-4 are garbage), 5 no prologue ramp in the loader.
-template <int MB, int WNB, int NSTAGE, int D, int LOADERS, int ABL = 0>
+// ADD: the form with an addend in the epilogue (mixq_gemm_w8a16_addend), an instantiation of its own: ADD = false is, instruction for
+// instruction, the kernel without the argument (the k loop sits at the edge of its register budget, and a run-time branch behind it moved
+// its register allocation and hazard padding).
+template <int MB, int WNB, int NSTAGE, int D, int LOADERS, int ABL = 0, bool ADD = false>
 __global__ __launch_bounds__((WO_CW + LOADERS) * 64) void gemm_w8a16_kernel(const WoArgs a)
 {
     constexpr int CW = WO_CW, NT = (CW + LOADERS) * 64;
@@ -303,6 +307,14 @@ __global__ __launch_bounds__((WO_CW + LOADERS) * 64) void gemm_w8a16_kernel(cons
         if constexpr (D > 4) prologue_w(std::integral_constant<int, 4>{});
         __builtin_amdgcn_s_barrier();                                            // B0: stage 0 landed
         __builtin_amdgcn_s_waitcnt(0xC07F);                                      // lgkmcnt(0): kernel arguments have long arrived (see gemm_wreg.hip)
+        // the addend's base and stride, held in scalar registers from here to the epilogue (opaque to the compiler: it would otherwise
+        // fetch them again by scalar loads placed inside the k loop)
+        const uint16_t* addp = nullptr;
+        int lda = 0;
+        if constexpr (ADD) {
+            addp = a.add; lda = a.lda;
+            asm volatile("" : "+s"(addp), "+s"(lda));
+        }
 #pragma unroll
         for (int j = 0; j < MB; ++j) xread(0, j, xoff0);
         wwait_rt(std::integral_constant<int, 0>{}, nk - 1);
@@ -352,8 +364,27 @@ __global__ __launch_bounds__((WO_CW + LOADERS) * 64) void gemm_w8a16_kernel(cons
             if constexpr (NSLOT > 5) tail_one(std::integral_constant<int, 5>{});
         }
 
-        // ---- epilogue: y = acc * scale_col[n] (+ bias[n]) -> fp16 tile in LDS ---------------------------------------
+        // ---- epilogue: y = acc * scale_col[n] (+ addend[m,n]) (+ bias[n]) -> fp16 tile in LDS -----------------------
         __builtin_amdgcn_s_waitcnt(0x0F70);                                      // vmcnt(0): nothing of this wave is in flight any more
+        // addend: the four consecutive channels a lane holds of a 16 x 16 block are ONE 8-byte load per (row block, column group),
+        // requested in front of the post-loop barrier - the registers of the weight ring are free from here on and the wait for the
+        // other waves covers the latency.  Nothing outside rows < M and columns < N is read: a row past M reads row M - 1 and a column
+        // group past N the last one, like the X rows and scale_col / bias (computed and dropped) - clamped, not predicated: a load
+        // under a per-lane condition becomes a branch with a wait of its own, and the loads would arrive one after the other.
+        u32x2 av[MB][WNB];
+        if constexpr (ADD) {
+            typedef const __attribute__((address_space(1))) u32x2* wo_gptr;      // (the opaque pointer lost its address space: global, not flat)
+#pragma unroll
+            for (int i = 0; i < WNB; ++i) {
+                const int n = n0 + wave * WN + i * 16 + lq * 4;
+                const int nc = n < a.N ? n : a.N - 4;
+#pragma unroll
+                for (int j = 0; j < MB; ++j) {
+                    int m = m0 + j * 16 + lm; m = m < a.M ? m : a.M - 1;
+                    av[j][i] = *(wo_gptr)(addp + static_cast<size_t>(m) * lda + nc);
+                }
+            }
+        }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                       // (the harmless past-the-end refills)
         __builtin_amdgcn_s_barrier();                                            // every wave is done reading the ring
         const bool has_bias = a.bias != nullptr;
@@ -370,10 +401,12 @@ __global__ __launch_bounds__((WO_CW + LOADERS) * 64) void gemm_w8a16_kernel(cons
             if (has_bias) unpack4(*reinterpret_cast<const u32x2_u*>(a.bias + nc), bv);
 #pragma unroll
             for (int j = 0; j < MB; ++j) {
-                float v[4];
+                float v[4], ad[4];
+                if constexpr (ADD) unpack4(av[j][i], ad);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     v[e] = acc[j][i][e] * swv[e];
+                    if constexpr (ADD) v[e] += ad[e];                        // the addend first, then the bias (include/mixq_hip.h)
                     if (has_bias) v[e] += bv[e];
                 }
                 u32x2 o;
@@ -493,6 +526,18 @@ __global__ __launch_bounds__(WSK * 64, 2) void gemm_w8a16_skinny_kernel(const Wo
         *reinterpret_cast<f32x4*>(lds + (wave * 4 + g) * 1024 + lane * 16) = f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
     __syncthreads();
     if (wave != 0) return;
+    // addend (block-uniform: absent, nothing is issued): one 8-byte load per column group, requested in front of the reduction's LDS reads;
+    // rows and column groups clamped as in the tiled kernel: nothing outside rows < M and columns < N is read
+    const int m = lr;
+    u32x2 av[4];
+    if (a.add) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int n = n0 + 4 * lh + 8 * g;
+            const int nc = n < a.N ? n : a.N - 4;
+            av[g] = *reinterpret_cast<const u32x2*>(a.add + static_cast<size_t>(xr) * a.lda + nc);      // (xr: the row clamped to M - 1)
+        }
+    }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         f32x4 s = *reinterpret_cast<const f32x4*>(lds + g * 1024 + lane * 16);
@@ -505,7 +550,6 @@ __global__ __launch_bounds__(WSK * 64, 2) void gemm_w8a16_skinny_kernel(const Wo
         o[0] = h2f(static_cast<uint16_t>(v.x & 0xffffu)); o[1] = h2f(static_cast<uint16_t>(v.x >> 16));
         o[2] = h2f(static_cast<uint16_t>(v.y & 0xffffu)); o[3] = h2f(static_cast<uint16_t>(v.y >> 16));
     };
-    const int m = lr;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         const int n = n0 + 4 * lh + 8 * g;
@@ -514,9 +558,14 @@ __global__ __launch_bounds__(WSK * 64, 2) void gemm_w8a16_skinny_kernel(const Wo
         unpack4(*reinterpret_cast<const u32x2_u*>(a.sw + nc), sv);
         if (a.bias) unpack4(*reinterpret_cast<const u32x2_u*>(a.bias + nc), bv);
         if (m < a.M && n < a.N) {
-            float v[4];
+            float v[4], ad[4];
+            if (a.add) unpack4(av[g], ad);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { v[e] = acc[4 * g + e] * sv[e]; if (a.bias) v[e] += bv[e]; }
+            for (int e = 0; e < 4; ++e) {
+                v[e] = acc[4 * g + e] * sv[e];
+                if (a.add) v[e] += ad[e];                                        // the addend first, then the bias, like the tiled kernel
+                if (a.bias) v[e] += bv[e];
+            }
             u32x2 o;
             o.x = static_cast<uint32_t>(f2h(v[0])) | (static_cast<uint32_t>(f2h(v[1])) << 16);
             o.y = static_cast<uint32_t>(f2h(v[2])) | (static_cast<uint32_t>(f2h(v[3])) << 16);
@@ -556,8 +605,11 @@ __global__ __launch_bounds__(256) void pack_w8a16_kernel(const int8_t* __restric
 struct WoConfig {
     const char* name; int mb, wnb, nstage, loaders;
     void (*k)(const WoArgs);
+    void (*ka)(const WoArgs);                          // the form with an addend (null: an ablation form, which has none)
 };
-#define MIXQ_WO(MBv, WNBv, NS, Dv, LD, ABL, TAG) { "w8a16_" TAG, MBv, WNBv, NS, LD, gemm_w8a16_kernel<MBv, WNBv, NS, Dv, LD, ABL> }
+#define MIXQ_WO(MBv, WNBv, NS, Dv, LD, ABL, TAG)                                                                                  \
+    { "w8a16_" TAG, MBv, WNBv, NS, LD, gemm_w8a16_kernel<MBv, WNBv, NS, Dv, LD, ABL>,                                             \
+      ABL == 0 ? gemm_w8a16_kernel<MBv, WNBv, NS, Dv, LD, 0, true> : nullptr }
 const WoConfig g_wo[] = {
     // name = tile (token rows x channels) _ X ring depth _ weight ring depth _ loader waves
     MIXQ_WO(8, 3, 8, 3, 2, 0, "128x192_s8_d3_l2"),     // 0
@@ -617,17 +669,18 @@ extern "C" int mixq_pack_w8a16(const int8_t* q_weight_kn, uint8_t* packed, int K
     return mixq_launch_status();
 }
 
-extern "C" int mixq_gemm_w8a16(const uint16_t* x, int ldx, const uint8_t* w_packed, const uint16_t* scale_col, const uint16_t* bias,
-                               uint16_t* y, int ldy, int M, int N, int K, mixq_stream_t stream)
+extern "C" int mixq_gemm_w8a16_addend(const uint16_t* x, int ldx, const uint8_t* w_packed, const uint16_t* scale_col, const uint16_t* addend,
+                                      int lda, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int K, mixq_stream_t stream)
 {
     if (M < 0 || N < 0 || K <= 0 || (M > 0 && N > 0 && (!x || !w_packed || !scale_col || !y))) return MIXQ_EINVAL;
-    if ((K % 64) || (N & 3) || (ldy & 3) || ldy < N || ldx < K || (ldx & 7)) return MIXQ_ESHAPE;
-    if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(y) & 7)) return MIXQ_EINVAL;
+    if ((K % 64) || (N & 3) || (ldy & 3) || ldy < N || ldx < K || (ldx & 7) || (addend && (lda < N || (lda & 3)))) return MIXQ_ESHAPE;
+    if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(y) & 7) || (reinterpret_cast<uintptr_t>(addend) & 7)) return MIXQ_EINVAL;
     if (M == 0 || N == 0) return MIXQ_OK;
     const int g_wo_forced = g_wo_forced_dev.get();
     WoArgs a;
     a.x = x; a.w = w_packed; a.sw = scale_col; a.bias = bias; a.y = y;
     a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldy = ldy; a.tiles_m = a.tiles_n = 0; a.wblocks = (N + 15) >> 4;
+    a.add = addend; a.lda = addend ? lda : 0;
     if (g_wo_forced == NUM_WO) {                                                 // the in-workgroup K-split form: explicit only (slower, see WO_SMALL)
         if (M > 32) return MIXQ_EINVAL;
         hipLaunchKernelGGL(gemm_w8a16_skinny_kernel, dim3((N + 31) / 32), dim3(WSK * 64), 0, mixq_stream(stream), a);
@@ -639,9 +692,17 @@ extern "C" int mixq_gemm_w8a16(const uint16_t* x, int ldx, const uint8_t* w_pack
     a.tiles_m = wo_cdiv(M, bm); a.tiles_n = wo_cdiv(N, bn);
     const size_t ring = static_cast<size_t>(g.nstage) * g.mb * 2048, stg = static_cast<size_t>(bm) * (bn * 2 + 16);
     const size_t shm = ring > stg ? ring : stg;
-    if (int rc = mixq_ensure_dynamic_lds(reinterpret_cast<const void*>(g.k), shm)) return rc;
-    hipLaunchKernelGGL(g.k, dim3(a.tiles_m * a.tiles_n), dim3((WO_CW + g.loaders) * 64), shm, mixq_stream(stream), a);
+    void (*const kern)(const WoArgs) = addend ? g.ka : g.k;
+    if (!kern) return MIXQ_EINVAL;
+    if (int rc = mixq_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), shm)) return rc;
+    hipLaunchKernelGGL(kern, dim3(a.tiles_m * a.tiles_n), dim3((WO_CW + g.loaders) * 64), shm, mixq_stream(stream), a);
     return mixq_launch_status();
+}
+
+extern "C" int mixq_gemm_w8a16(const uint16_t* x, int ldx, const uint8_t* w_packed, const uint16_t* scale_col, const uint16_t* bias,
+                               uint16_t* y, int ldy, int M, int N, int K, mixq_stream_t stream)
+{
+    return mixq_gemm_w8a16_addend(x, ldx, w_packed, scale_col, nullptr, 0, bias, y, ldy, M, N, K, stream);
 }
 
 extern "C" int mixq_gemm_w8a16_set_config(int cfg) {

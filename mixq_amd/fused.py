@@ -268,17 +268,21 @@ class MixLlamaMLP(nn.Module):
         return out
 
     @torch.no_grad()
-    def forward(self, x):
+    def forward(self, x, residual=None):
+        """`residual` (an extension; x.shape[:-1] + (out_features,), the model's dtype, on x's device): out = residual + down_proj(silu(gate) * up)
+        with the add in down_proj's GEMM epilogue - one rounding, no pass of its own (MixLinear_GEMM.forward: `residual`) - on the joint and
+        the two-launch route alike, with and without the row-maximum hand-over.  The reference adds it in torch (modules/fused/block.py:33)."""
+        radd = {} if residual is None else {"residual": residual}
         rows = x.numel() // x.shape[-1]
         if not self.up_proj_._small_batch_image(rows) and self._joint_applies(self.MLPCache):
             # silu(gate(x)) * up(x) from ONE launch over the two layers' interleaved rows (mlp.py:57-63), bit-identical to the route below
-            return self.down_proj_(self._forward_joint(x, self.MLPCache), None, True)
+            return self.down_proj_(self._forward_joint(x, self.MLPCache), None, True, **radd)
         up_output = self.up_proj_(x, self.MLPCache)
         # silu(gate(x)) * up(x) in gate_proj's epilogue (the reference multiplies in a separate pass, mlp.py:61-63)
         # ... and down_proj's pre-pass row maxima leave the same epilogue (its quantiser then needs one pass over the activation)
         extra = {"amax_for": self.down_proj_} if self.config.fuse_down_amax else {}
         gate_output = self.gate_proj_.forward_without_preconditionFusedSilu(x, self.MLPCache, mul=up_output, **extra)
-        return self.down_proj_(gate_output, None, True)
+        return self.down_proj_(gate_output, None, True, **radd)
 
 
 class MixFalconMLP(nn.Module):

@@ -644,9 +644,38 @@ class MixLinear_GEMM(nn.Module):
         return _backend.ForwardPlan(M, self.out_features, self.in_features, self.bit, self._sigma_f, inputs.stride(0), ind_buf, n, n_dev,
                                     cache.x_scale, wpk, self.scale_col, wo, self.bias, self.x_fmt(M), kept_mask=self._col_mask() if n else None, **extra)
 
+    def _residual_rows(self, x, residual):
+        """`residual` of forward() as the GEMM's [M, N] addend, or a RuntimeError that names the argument: no silent conversion."""
+        want = tuple(x.shape[:-1]) + (self.out_features,)
+        dt = str(self.act_dtype).replace("torch.", "")
+        if not isinstance(residual, Tensor):
+            raise RuntimeError(f"MixLinear_GEMM: residual must be a {dt} tensor of shape {want}, got {type(residual).__name__}")
+        if residual.dtype != self.act_dtype:
+            raise RuntimeError(f"MixLinear_GEMM: residual must be {dt} like the layer's activations (MixqConfig.act_dtype), got {residual.dtype}")
+        if tuple(residual.shape) != want:
+            raise RuntimeError(f"MixLinear_GEMM: residual must have shape {want} (x.shape[:-1] + (out_features,)), got {tuple(residual.shape)}")
+        if not residual.is_cuda or residual.device != x.device:
+            raise RuntimeError(f"MixLinear_GEMM: residual must be a GPU (HIP) tensor on x's device ({x.device}), got {residual.device}")
+        if residual.stride(-1) != 1:
+            raise RuntimeError(f"MixLinear_GEMM: residual must have a contiguous last dimension, got strides {tuple(residual.stride())}")
+        r = residual.reshape(-1, self.out_features)
+        if r.shape[0] > 1 and (r.stride(0) % 4 or r.stride(0) < self.out_features):
+            raise RuntimeError(f"MixLinear_GEMM: residual needs a row stride that is a multiple of 4 elements and at least out_features = "
+                               f"{self.out_features}, got {r.stride(0)}")
+        return r
+
     # ------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def forward(self, x, cache=None, unfused=False):
+    def forward(self, x, cache=None, unfused=False, residual=None):
+        """`residual` (an extension: the reference adds it in torch, modules/fused/block.py:32-33): a tensor of shape
+        x.shape[:-1] + (out_features,), of the layer's act_dtype (float16 for a weight-only layer), on x's device, with a contiguous last
+        dimension - anything else raises RuntimeError.  It is the addend of the GEMM's fp32 epilogue, y = round(linear(x) + residual) with
+        ONE rounding and no pass of its own, on every route: search phase / two calls, the frozen one-call forward, weight-only.  The
+        result is a new tensor; the residual is only read (it should not be x itself: new outlier columns of x are zeroed in place).
+        It is a per-call pointer like x - not part of the kept argument block's identity (_frozen_key) - and under hipGraph capture its
+        address is baked into the graph exactly as x's is: replay with new contents in the same buffer."""
+        res = None if residual is None else self._residual_rows(x, residual)
+        radd = {} if res is None else {"addend": res}         # (handed on only when given: a call without it is the call it always was)
         if cache is None:
             cache = self.cache
         cache.shape = x.shape[:-1] + (self.out_features,)
@@ -683,10 +712,10 @@ class MixLinear_GEMM(nn.Module):
                 tag = getattr(x, "_mixq_row_amax", None)     # left by the GEMM that produced x (forward_without_preconditionFusedSilu)
                 if tag is not None and tag[1] is self and self._amax_dirty and tag[0] is self._amax_buf and tag[0].numel() >= M \
                         and tag[2] == x._version:            # (an in-place edit of x since the GEMM wrote it makes the maxima stale)
-                    y1, cache.q_xcache, xo = plan.run(inputs, row_amax=tag[0], col_mask=self._col_mask())
+                    y1, cache.q_xcache, xo = plan.run(inputs, row_amax=tag[0], col_mask=self._col_mask(), **radd)
                     self._amax_dirty = False                 # the quantiser cleared the buffer
                 else:
-                    y1, cache.q_xcache, xo = plan.run(inputs)
+                    y1, cache.q_xcache, xo = plan.run(inputs, **radd)
                 if xo is not None:
                     cache.activation_outliers = xo
                 cache.n_dev = plan.keep[1]
@@ -697,7 +726,7 @@ class MixLinear_GEMM(nn.Module):
             key = (id(self.q_weight), self.q_weight.data_ptr(), self.q_weight._version)
             if self._wpk is None or self._wpk_key != key:
                 self._wpk, self._wpk_key = _backend.PackW8A16(self.q_weight), key
-            y = _backend.W8A16Linear(inputs, self._wpk, self.scale_col, self.bias, self.out_features, self.in_features)
+            y = _backend.W8A16Linear(inputs, self._wpk, self.scale_col, self.bias, self.out_features, self.in_features, **radd)
             return y.reshape(cache.shape)
         qmax = 2 ** (self.bit - 1) - 1
 
@@ -737,7 +766,7 @@ class MixLinear_GEMM(nn.Module):
             if self.cnt >= self.cache.stop or self.ind.shape[0] > 128:
                 self.add_outliers = False
 
-        y1 = self._gemm(cache, M, ACT_NONE)
+        y1 = self._gemm(cache, M, ACT_NONE, **radd)
         if self.config.compact_weights and not self.add_outliers:
             self.compact_weights_()
         return y1.reshape(cache.shape)

@@ -912,11 +912,24 @@ class ForwardPlan:
         self.captured = False                          # ran under hipGraph capture: a graph out there replays the addresses this plan carries
         self.q_shape, self.q_dtype = (packed_rows(M) if qfmt else M, _q_row_bytes(K, bit, qfmt)), (torch.int8 if bit == 8 else torch.uint8)
 
-    def run(self, x, row_amax=None, col_mask=None):
+    def run(self, x, row_amax=None, col_mask=None, addend=None):
         """x: [M,K] in the plan's dtype with the row stride the plan was built for.  Returns (y [M,N], q_x, x_out [M,n] or None).
         row_amax (int32 [>= M] on the device): the rows' masked maxima left by the GEMM that produced x (FusedLinear(row_amax=...));
-        the quantise pass is then the one-pass known-maximum kernel, which also clears the buffer."""
+        the quantise pass is then the one-pass known-maximum kernel, which also clears the buffer.
+        addend ([M,N] in the plan's dtype, on its device, contiguous last dimension, row stride a multiple of 4 elements; read only): enters
+        the GEMM's fp32 epilogue in front of the one rounding (include/mixq_hip.h: z = acc sx sw + sum xo wo + addend) - the residual stream
+        of a decoder layer.  A per-call pointer like x: the block's addend / lda are written on EVERY call (None: NULL / 0), so a plan that
+        ran with a residual never replays its address; under hipGraph capture the address is baked into the graph exactly as x's is."""
         dev = self.device
+        ap, lda = None, 0
+        if addend is not None:
+            if not isinstance(addend, torch.Tensor) or addend.device != dev:
+                raise RuntimeError(f"ForwardPlan: addend lives on {getattr(addend, 'device', type(addend).__name__)}, the plan was built for {dev}")
+            if addend.dtype != self.dtype or addend.dim() != 2 or tuple(addend.shape) != (self.M, self.N) or addend.stride(1) != 1 or (self.M > 1 and addend.stride(0) % 4):
+                raise RuntimeError(f"ForwardPlan: addend must be {str(self.dtype).replace('torch.', '')} [{self.M}, {self.N}] with a contiguous last dimension and a row "
+                                   f"stride that is a multiple of 4 elements (got {addend.dtype} {tuple(addend.shape)} strides {tuple(addend.stride())})")
+            addend = _aligned_addend(addend)                 # (a base that is not 8-byte aligned: through a copy, as in FusedLinear)
+            ap, lda = addend.data_ptr(), (addend.stride(0) if self.M > 1 else self.N)      # (one row: any stride describes it)
         if col_mask is not None and col_mask is not self.kept_mask:
             _dev_check(col_mask)
             _check_kept_map(col_mask, self.K, "ForwardPlan.run")
@@ -937,6 +950,7 @@ class ForwardPlan:
         with self.lock:
             cm = col_mask if col_mask is not None else self.kept_mask
             a.row_amax, a.col_mask, a.col_mask_words = _ptr(row_amax), _ptr(cm), (0 if cm is None else cm.numel())
+            a.addend, a.lda = ap, lda                        # every call: never the pointer of an earlier one
             if xo is not None:
                 a.x_out = xo.data_ptr()
             a.x, a.q_x, a.y = x.data_ptr(), q.data_ptr(), y.data_ptr()
@@ -1022,9 +1036,21 @@ def PackW8A16(q_weight_kn):
     return out
 
 
-def W8A16Linear(x, w_packed, scale_col, bias, N, K, out=None):
-    """y = x @ (q * scale_col) + bias with the weights from PackW8A16.  x fp16 [M,K] (row stride % 8 == 0)."""
-    _dev_check(x, w_packed, scale_col, bias)
+def _overlap(a, b):
+    """Do the byte ranges two 2-D tensors span intersect?"""
+    def span(t):
+        n = sum((d - 1) * st for d, st in zip(t.shape, t.stride())) + 1 if t.numel() else 0
+        return t.data_ptr(), t.data_ptr() + n * t.element_size()
+    (a0, a1), (b0, b1) = span(a), span(b)
+    return a0 < b1 and b0 < a1
+
+
+def W8A16Linear(x, w_packed, scale_col, bias, N, K, out=None, addend=None):
+    """y = x @ (q * scale_col) (+ addend) + bias with the weights from PackW8A16.  x fp16 [M,K] (row stride % 8 == 0).
+    addend (fp16 [M,N] on x's device, contiguous last dimension, row stride >= N and a multiple of 4 elements; read only): added in
+    the GEMM's fp32 epilogue in front of the bias and the ONE rounding (mixq_gemm_w8a16_addend) - the residual stream behind a weight-only
+    down_proj / fc_out.  It may not overlap `out`.  Without it the call is mixq_gemm_w8a16, as before."""
+    _dev_check(x, w_packed, scale_col, bias, addend)
     if x.dtype != torch.float16 or scale_col.dtype != torch.float16:
         raise RuntimeError("W8A16Linear: x and scale_col must be float16")
     x2 = x.reshape(-1, x.shape[-1])
@@ -1038,6 +1064,19 @@ def W8A16Linear(x, w_packed, scale_col, bias, N, K, out=None):
         if out.dtype != torch.float16:
             raise RuntimeError(f"W8A16Linear: `out` must be torch.float16, got {out.dtype}")
         _check_out(out, M, N, x.device, "W8A16Linear")
+    if addend is not None:
+        if addend.dtype != torch.float16 or addend.device != x.device:
+            raise RuntimeError(f"W8A16Linear: addend must be torch.float16 on x's device ({x.device}), got {addend.dtype} on {addend.device}")
+        if addend.dim() != 2 or tuple(addend.shape) != (M, N) or addend.stride(1) != 1 or (M > 1 and (addend.stride(0) % 4 or addend.stride(0) < N)):
+            raise RuntimeError(f"W8A16Linear: addend must be [{M}, {N}] with a contiguous last dimension and a row stride that is a multiple of 4 elements "
+                               f"and at least {N} (got {tuple(addend.shape)} strides {tuple(addend.stride())})")
+        if out is not None and _overlap(addend, out):
+            raise RuntimeError("W8A16Linear: addend may not alias `out` (include/mixq_hip.h: mixq_gemm_w8a16_addend)")
+        addend = _aligned_addend(addend)
+        lda = addend.stride(0) if M > 1 else N               # (one row: any stride describes it)
+        _capi.call("mixq_gemm_w8a16_addend", x2.data_ptr(), x2.stride(0) if M else K, w_packed.data_ptr(), scale_col.data_ptr(), addend.data_ptr(),
+                   lda, _ptr(bias), y.data_ptr(), y.stride(0) if M else N, M, N, K, _stream())
+        return y
     _capi.call("mixq_gemm_w8a16", x2.data_ptr(), x2.stride(0) if M else K, w_packed.data_ptr(), scale_col.data_ptr(), _ptr(bias),
                y.data_ptr(), y.stride(0) if M else N, M, N, K, _stream())
     return y

@@ -4,7 +4,7 @@
 // the plan / workspace / per-device tables, launch-geometry arithmetic) for out-of-bounds accesses or use-after-free.
 // What it walks: identification, every quantise / detect / dequant / re-tile entry point incl. empty inputs and rejected arguments, the
 // kept-outlier-map routes, the fused GEMMs on every operand layout, mixq_linear_forward on a KEPT argument block (re-used, then edited),
-// the RMSNorm entry points, the W8A16 pair - each followed by a device synchronise, results cross-checked where a second route exists.
+// the RMSNorm entry points, the W8A16 pair and its addend form - each followed by a device synchronise, results cross-checked where a second route exists.
 //   build + run: tools/asan_capi.sh (on the GPU box)            exit code 0 and no ASAN report = clean
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -199,6 +199,25 @@ int main() {
     CHECK(mixq_gemm_w8a16(x.p, K, w16.p, sw.p, bias.p, y3.p, N, M, N, K, nullptr) == MIXQ_OK);
     CHECK(mixq_gemm_w8a16(x.p, K, w16.p, sw.p, bias.p, y3.p, N, 1, N, K, nullptr) == MIXQ_OK);
     CHECK(mixq_gemm_w8a16(x.p, K, w16.p, sw.p, bias.p, y3.p, N, M, N, 100, nullptr) == MIXQ_ESHAPE);
+    HIPOK(hipDeviceSynchronize());
+    // ... with an addend (ABI 1.3): NULL is the call above, a zero addend with a pad (lda = N + 8) leaves its bytes; stride, pointer, M == 0
+    CHECK(mixq_gemm_w8a16(x.p, K, w16.p, sw.p, bias.p, y3.p, N, M, N, K, nullptr) == MIXQ_OK);
+    CHECK(mixq_gemm_w8a16_addend(x.p, K, w16.p, sw.p, nullptr, 0, bias.p, y2.p, N, M, N, K, nullptr) == MIXQ_OK);
+    HIPOK(hipDeviceSynchronize());
+    CHECK(y2.down() == y3.down());
+    Dev<uint16_t> add(static_cast<size_t>(M) * (N + 8));                       // (zero-filled)
+    CHECK(mixq_gemm_w8a16_addend(x.p, K, w16.p, sw.p, add.p, N + 8, bias.p, y2.p, N, M, N, K, nullptr) == MIXQ_OK);
+    HIPOK(hipDeviceSynchronize());
+    CHECK(y2.down() == y3.down());
+    CHECK(mixq_gemm_w8a16_addend(x.p, K, w16.p, sw.p, add.p, N + 8, bias.p, y2.p, N, 1, N, K, nullptr) == MIXQ_OK);
+    CHECK(mixq_gemm_w8a16_addend(x.p, K, w16.p, sw.p, add.p, N + 8, bias.p, y2.p, N, 0, N, K, nullptr) == MIXQ_OK);
+    CHECK(mixq_gemm_w8a16_addend(x.p, K, w16.p, sw.p, add.p, N - 4, bias.p, y2.p, N, M, N, K, nullptr) == MIXQ_ESHAPE);       // lda < N
+    CHECK(mixq_gemm_w8a16_addend(x.p, K, w16.p, sw.p, add.p, N + 2, bias.p, y2.p, N, M, N, K, nullptr) == MIXQ_ESHAPE);       // lda % 4
+    CHECK(mixq_gemm_w8a16_addend(x.p, K, w16.p, sw.p, add.p, N - 4, bias.p, y2.p, N, 0, N, K, nullptr) == MIXQ_ESHAPE);       // ... checked at M == 0 too
+    CHECK(mixq_gemm_w8a16_addend(x.p, K, w16.p, sw.p, add.p + 2, N + 8, bias.p, y2.p, N, M, N, K, nullptr) == MIXQ_EINVAL);   // base 4-byte aligned
+    CHECK(mixq_gemm_w8a16_addend(x.p, K, w16.p, sw.p, add.p + 2, N + 8, bias.p, y2.p, N, 0, N, K, nullptr) == MIXQ_EINVAL);
+    CHECK(mixq_gemm_w8a16_addend(x.p, K, w16.p, sw.p, add.p + 2, N - 4, bias.p, y2.p, N, M, N, 100, nullptr) == MIXQ_ESHAPE);  // K % 64 with a bad addend: as without
+    CHECK(mixq_gemm_w8a16_addend(nullptr, K, w16.p, sw.p, add.p, N + 8, bias.p, y2.p, N, M, N, K, nullptr) == MIXQ_EINVAL);
     HIPOK(hipDeviceSynchronize());
 
     printf(g_fail ? "asan_capi: %d check(s) FAILED\n" : "asan_capi: all checks passed\n", g_fail);

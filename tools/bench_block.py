@@ -9,7 +9,12 @@ modules/fused/attn.py:219,263, modules/fused/mlp.py:57-70), at 512 tokens:
 over `--layers` independent copies of the weights (32 x 202 MB = 6.5 GB for the 7b shapes): launch i of the graph runs layer i % layers, so
 every layer's weights come from HBM, as in a model - and, for comparison, over ONE copy (everything resident in the 256 MB memory-side cache
 after the first pass, as in a single-layer benchmark loop).  Measurement protocol: bench.conditioned_replay.  A per-kernel breakdown comes
-from running this script under `rocprofv3 --kernel-trace --stats` (round 4's evidence script did, into profiles/r04_block_kernels.txt)."""
+from running this script under `rocprofv3 --kernel-trace --stats` (round 4's evidence script did, into profiles/r04_block_kernels.txt).
+
+--residual: the same path WITH the layer's two residual adds (modules/fused/block.py:32-33: h = x + o_proj(attn); out = h + mlp(norm_2(h))), in two
+forms captured in the same process - "torch": the adds as torch kernels behind o_proj and the MLP (what a caller had to write before
+`residual=`), "fused": `o_proj(attn, None, True, residual=x)` and `mlp(norm_2(h), residual=h)`, the adds in the two GEMM epilogues - and timed
+under the same protocol in alternating rounds (--rounds), each round one conditioned_replay per form; median and spread over the rounds."""
 import argparse
 import os
 import sys
@@ -44,13 +49,55 @@ class Layer:
         self.norm1.next_layer, self.norm2.next_layer = self.W_pack, up
         self.H = H
 
-    def __call__(self, x):
+    def __call__(self, x, residual=None):
+        """residual: None (the path without the residual stream), "torch" (two torch adds) or "fused" (`residual=`: the GEMM epilogues)."""
         h = self.norm1(x)
         qkv = self.W_pack(h)                                                    # (cache filled by the norm: unfused=False)
         attn = qkv[:, :self.H].contiguous()                                     # stand-in for the attention output (out of scope)
+        if residual == "fused":
+            hs = self.o_proj(attn, None, True, residual=x)
+            return self.mlp(self.norm2(hs), residual=hs)
         o = self.o_proj(attn, None, True)
+        if residual == "torch":
+            hs = x + o
+            return hs + self.mlp(self.norm2(hs))
         h2 = self.norm2(o)
         return self.mlp(h2)
+
+
+def residual_arms(layers, nl, label, steps, xs, base, side):
+    """The two forms of the residual stream on the same layers and inputs: one graph each, replayed in alternating rounds."""
+    import statistics
+    restore = lambda: xs.copy_(base.unsqueeze(0).expand_as(xs))
+    with torch.no_grad():
+        a, b = layers[0](base.clone(), "torch"), layers[0](base.clone(), "fused")
+        torch.cuda.synchronize()
+        diff = float((a.float() - b.float()).abs().max())
+    graphs = {}
+    with torch.cuda.stream(side):
+        for form in ("torch", "fused"):
+            restore()
+            side.synchronize()
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr, stream=side):
+                for i in range(steps):
+                    layers[i % nl](xs[i], form)
+            torch.cuda.synchronize()
+            graphs[form] = gr
+        times = {form: [] for form in graphs}
+        for _ in range(ROUNDS):
+            for form, gr in graphs.items():
+                ms, _, _ = bench.conditioned_replay(gr, side, restore=restore)
+                times[form].append(ms * 1e3 / steps)
+    print(f"  {label}, with the two residual adds; {ROUNDS} alternating rounds, us per layer (max |torch - fused| = {diff:.3g}):")
+    for form, t in times.items():
+        print(f"    {form:6s} median {statistics.median(t):7.1f}   min {min(t):7.1f}   max {max(t):7.1f}   spread {max(t) - min(t):5.1f}   rounds: "
+              + " ".join(f"{v:.1f}" for v in t), flush=True)
+    d = statistics.median(times["torch"]) - statistics.median(times["fused"])
+    print(f"    residual= saves {d:+.1f} us per layer against the torch adds (spread of the torch form: {max(times['torch']) - min(times['torch']):.1f} us)", flush=True)
+
+
+ROUNDS = 5
 
 
 def main():
@@ -59,7 +106,11 @@ def main():
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--bit", type=int, default=8)
     ap.add_argument("--passes", type=int, default=2, help="passes over all layers per graph")
+    ap.add_argument("--residual", action="store_true", help="the path with its two residual adds: torch adds against residual= (alternating rounds)")
+    ap.add_argument("--rounds", type=int, default=5, help="--residual: alternating rounds of one conditioned_replay per form")
     args = ap.parse_args()
+    global ROUNDS
+    ROUNDS = args.rounds
     dev = "cuda"
     M, H, F, QKV = args.M, 4096, 11008, 12288
     cache = MixLibCache(M, sigma=6, bit=args.bit, device=dev)
@@ -85,6 +136,11 @@ def main():
         steps = max(nl * args.passes, 16)
         xs = base.unsqueeze(0).repeat(steps, 1, 1).contiguous()
         side = torch.cuda.Stream()
+        if args.residual:
+            residual_arms(layers, nl, label, steps, xs, base, side)
+            del layers, xs
+            torch.cuda.empty_cache()
+            continue
         with torch.cuda.stream(side):
             gr = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gr, stream=side):
