@@ -144,8 +144,23 @@ int mixq_device_info(char* buf_host, int cap);
  * mixq_quant_known_amax_bf16.  Pad columns of x_out / w_out (>= n_out) may hold anything, NaN patterns included: they are masked.
  * Served layouts: MIXQ_X_PACKED | MIXQ_W_F16X64 (int8) and MIXQ_XW_F6X128 (4-bit), at every batch size, by the weights-in-registers
  * kernels; plain / P16X64 layouts, nibble-packed int4 and MIXQ_ACT_SILU_PAIR answer MIXQ_ESHAPE.  A configuration forced with
- * mixq_gemm_set_config that has no bf16 form answers MIXQ_EINVAL before any launch.  Not (yet) in bf16: mixq_rmsnorm*,
- * mixq_gemm_w8a16, mixq_gemm_i8 / mixq_dequant. */
+ * mixq_gemm_set_config that has no bf16 form answers MIXQ_EINVAL before any launch.  Not (yet) in bf16: mixq_gemm_w8a16,
+ * mixq_gemm_i8 / mixq_dequant, and MIXQ_ACT_SILU_PAIR (the joint gate / up launch stays fp16 only).
+ *
+ * ---- bf16 RMSNorm (ABI 1.4): mixq_rmsnorm_bf16, mixq_rmsnorm_quant_fused_bf16, mixq_rmsnorm_quant_fused_masked_bf16 ----
+ * The argument lists of their fp16 twins ("RMSNorm in front of the path" below); x, weight, out and x_out hold bfloat16, x_scale stays
+ * fp16, q and its formats are unchanged (8-bit: PLAIN, P16X64, F16X64; 4-bit: PLAIN, P16X64, F6X128, R6X128).  The arithmetic is fixed by
+ * decision - the fp16 contract with the container swapped:
+ *   ss      thread t of 256 takes the row's 16-byte chunks t, t + 256, ... element by element, each step ss = fmaf(v, v, ss) in fp32 (a
+ *           bf16 square is exact in fp32, so the fma equals a rounded add); 64-lane butterfly (xor 32, 16, 8, 4, 2, 1); (w0 + w1) + (w2 + w3)
+ *   inv     = 1 / sqrtf(ss / K + eps), IEEE fp32 divide and sqrt
+ *   y       = RNE_bf16( fp32( fp32(float(x) * inv) * float(weight) ) ): two fp32 roundings, then one to bfloat16
+ *   fused forms: x_out[:, j] = y[:, ind[j]], those columns zeroed in `out`; x_scale and q from the zeroed row exactly as
+ *   mixq_find_row_scale_bf16 computes them; the same misprediction predicate; the kept-map form keeps its fallback for a map built for
+ *   another count than the live one, the K <= 30000 limit and the n_dev live count.
+ * Supported range: a row whose inlier maximum exceeds 65504 * qmax has no finite fp16 scale (as above); a bf16 row can also hold values
+ * whose squares overflow fp32 - rows whose sum of squares is not finite are outside the supported range.
+ * mixq_version() still answers 1003: the number is pinned behaviour of the 1.3 suite; probe for the three symbols instead. */
 
 /* ---- (i) per-token absmax + quantise ------------------------------------------------------------------
  * Replaces mixlib.FindRowScale(x, x_scale, M, K, bit) -> q_x   (linear.py:190-193, :221).
@@ -370,15 +385,27 @@ int mixq_dequant(const int32_t* y32, int ldy32, const uint16_t* x_scale, const u
  *   x fp16 [M,K] ldx, weight fp16 [K], out fp16 [M,K] ldout; K % 8 == 0, K <= 32768. */
 int mixq_rmsnorm(const uint16_t* x, const uint16_t* weight, uint16_t* out, int M, int K, int ldx, int ldout, float eps,
                  mixq_stream_t stream);
+/* x, weight, out: bfloat16 ("bf16 RMSNorm" above) */
+int mixq_rmsnorm_bf16(const uint16_t* x, const uint16_t* weight, uint16_t* out, int M, int K, int ldx, int ldout, float eps,
+                      mixq_stream_t stream);
 int mixq_rmsnorm_quant_fused(const uint16_t* x, const uint16_t* weight, uint16_t* out, const int32_t* ind, int n,
                              const int32_t* n_dev, uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag,
                              int M, int K, int ldx, int ldout, int ldxo, float eps, int bit, float sigma, int qfmt,
                              mixq_stream_t stream);
+/* x, weight, out, x_out: bfloat16; x_scale: fp16 */
+int mixq_rmsnorm_quant_fused_bf16(const uint16_t* x, const uint16_t* weight, uint16_t* out, const int32_t* ind, int n,
+                                  const int32_t* n_dev, uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag,
+                                  int M, int K, int ldx, int ldout, int ldxo, float eps, int bit, float sigma, int qfmt,
+                                  mixq_stream_t stream);
 /* ... with the next layer's kept outlier map (layout: mixq_quant_fused_masked): same bytes out */
 int mixq_rmsnorm_quant_fused_masked(const uint16_t* x, const uint16_t* weight, uint16_t* out, const int32_t* ind, int n,
                                     const int32_t* n_dev, const uint32_t* col_mask, int map_words, uint16_t* x_scale, void* q, uint16_t* x_out,
                                     int32_t* flag, int M, int K, int ldx, int ldout, int ldxo, float eps, int bit, float sigma,
                                     int qfmt, mixq_stream_t stream);
+int mixq_rmsnorm_quant_fused_masked_bf16(const uint16_t* x, const uint16_t* weight, uint16_t* out, const int32_t* ind, int n,
+                                         const int32_t* n_dev, const uint32_t* col_mask, int map_words, uint16_t* x_scale, void* q, uint16_t* x_out,
+                                         int32_t* flag, int M, int K, int ldx, int ldout, int ldxo, float eps, int bit, float sigma,
+                                         int qfmt, mixq_stream_t stream);
 
 /* ---- weight-only W8A16 Linear -----------------------------------------------------
  * mixq_gemm_w8a16 replaces EETQ's w8_a16_gemm(x, q_weight, scale_col) as called at modules/linear.py:178-184:

@@ -99,8 +99,9 @@ SIGNATURES = {
     "mixq_gemm_amax_supported": [_I, _I, _I, _I],
     "mixq_quant_known_amax": [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
 }
-# the bfloat16-activation twins (ABI 1.1: the quantise side; 1.2: the GEMMs and the one-call forward): the same argument lists
-BF16_TWINS = ("mixq_find_row_scale", "mixq_extract_outliers_zero", "mixq_quant_fused", "mixq_quant_fused_masked", "mixq_detect_outlier_cols",
+# the bfloat16-activation twins (ABI 1.1: the quantise side; 1.2: the GEMMs and the one-call forward; 1.4: the RMSNorm forms): the same argument lists
+BF16_TWINS = ("mixq_rmsnorm", "mixq_rmsnorm_quant_fused", "mixq_rmsnorm_quant_fused_masked",
+              "mixq_find_row_scale", "mixq_extract_outliers_zero", "mixq_quant_fused", "mixq_quant_fused_masked", "mixq_detect_outlier_cols",
               "mixq_quant_known_amax", "mixq_selftest_quant_exact",
               "mixq_gemm_i8_fused", "mixq_gemm_i4_fused", "mixq_gemm_i8_fused_amax", "mixq_gemm_amax_supported", "mixq_linear_forward")
 SIGNATURES.update({name + "_bf16": SIGNATURES[name] for name in BF16_TWINS})

@@ -43,8 +43,15 @@ class MixqConfig:
     # The model's activation dtype: ONE per model.  A layer takes x of exactly this dtype and returns y in it (torch.float16, the
     # reference's, or torch.bfloat16: DESIGN.md section 2).  x_scale, scale_col, bias, sigma and the weight_cache buffer are float16 in
     # either case; y, x_out / activation_outliers and an addend / multiplier follow this switch.  Served in bfloat16: MixLinear_GEMM
-    # (W8A8 and W4A4); not (yet): weight_only layers, MixLlamaMLP's fused routes, the fused RMSNorm.
+    # (W8A8 and W4A4) and, behind `fused_bf16` below, FasterTransformerRMSNorm and MixLlamaMLP; not (yet): weight_only layers and the joint
+    # gate / up launch (a bfloat16 MixLlamaMLP runs up_proj's launch, then gate_proj's with the SiLU-and-multiply epilogue).
     act_dtype: torch.dtype = torch.float16
+    # Opt-in to the bfloat16 forms of the fused modules (fused.py): with act_dtype=torch.bfloat16 and fused_bf16=True,
+    # FasterTransformerRMSNorm runs the bf16 norm + extract + quantise pass (mixq_rmsnorm*_bf16) and MixLlamaMLP the two-launch route with the
+    # SiLU-and-multiply epilogue and the row-maximum hand-over to down_proj.  The default is off ONLY because the refusal of these modules
+    # under a bfloat16 config (NotImplementedError at construction) is pinned behaviour of this ABI minor; nothing else speaks against it.
+    # Without act_dtype=torch.bfloat16 the switch does nothing.  Not part of key(): it selects no GEMM plan and no weight image.
+    fused_bf16: bool = False
 
     def __post_init__(self):
         if self.act_dtype not in (torch.float16, torch.bfloat16):

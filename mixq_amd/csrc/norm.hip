@@ -12,6 +12,21 @@
 //   y[k]    = fp16( (float(x[k]) * inv_rms) * float(w[k]) )
 //   fused form: X_out[:, j] = y[:, ind[j]]; y[:, ind] = 0 in `out`; x_scale / q from the zeroed y exactly as
 //   mixq_find_row_scale does.
+//
+// bfloat16 (the `_bf16` entry points; BF = true below, as in quant.hip / common.h): x, weight, out and x_out hold bfloat16, x_scale stays
+// fp16, q and its formats are unchanged.  The contract is the one above with the container swapped (fixed by decision as well; restated in
+// numpy float32 by tests/bf16_norm_ref.py):
+//   ss      the same thread order, butterfly and wave sum; each step ss = fmaf(v, v, ss) in fp32.  A bf16 square is exact in fp32 (8-bit
+//           significands), so this fma equals a rounded add of the exact square.
+//   inv_rms = 1 / sqrtf(ss / K + eps)               (IEEE fp32 divide and sqrt)
+//   y[k]    = RNE_bf16( fp32( fp32(float(x[k]) * inv_rms) * float(w[k]) ) ): two fp32 roundings, then one to bf16 (the opaque barrier of
+//             norm1 stays: the last multiply and the conversion must not become one operation)
+//   fused form: as above; x_scale / q from the zeroed row exactly as mixq_find_row_scale_bf16 computes them (the IEEE division of
+//   mixq_row_scale<true>; the row maximum is the packed 16-bit-pattern maximum, monotone for finite bf16 too); the same flag predicate;
+//   the kept-map route keeps its `mcount == n` fallback, the K <= 30000 limit and the n_dev live count.
+// Supported range: as for every bf16 quantise pass a row whose inlier maximum exceeds 65504 * qmax has no finite fp16 scale; and a bf16
+// row can hold values whose squares overflow fp32 - rows whose ss is not finite are outside the supported range (no code for them).
+// The fp16 instantiations are the code they were (profiles/bf16_norm_code_objects.txt compares the instruction streams).
 #include "common.h"
 
 namespace {
@@ -22,10 +37,13 @@ typedef unsigned short us2n_t __attribute__((ext_vector_type(2)));
 // y = fp16( fp32(fp32(x * inv) * w) ): every product is rounded to fp32 before the next step.  Written with the _rn
 // intrinsics and an opaque barrier so the compiler cannot fold the last multiply and the conversion into one
 // v_fma_mixlo_f16 (a single rounding of the exact product, which differs from the contract in ~1 of 30k elements).
+// BF: the same two fp32 products from bfloat16 operands, then ONE round-to-nearest-even to bfloat16 (v_cvt_pk_bf16_f32).
+template <bool BF>
 __device__ __forceinline__ uint16_t norm1(uint16_t x, float inv, uint16_t w) {
-    float t = __fmul_rn(__fmul_rn(h2f(x), inv), h2f(w));
+    float t = __fmul_rn(__fmul_rn(a2f<BF>(x), inv), a2f<BF>(w));
     asm volatile("" : "+v"(t));
-    return f2h(t);
+    if constexpr (BF) return __builtin_bit_cast(uint16_t, static_cast<__bf16>(t));
+    else return f2h(t);
 }
 
 __device__ __forceinline__ float block_sum_ordered(float v, float* red) {
@@ -45,7 +63,8 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
-template <int BIT, int NCH, bool QUANT>
+// BF: x, w, out and x_out hold bfloat16 instead of fp16 (common.h a2f); x_scale stays fp16
+template <int BIT, int NCH, bool QUANT, bool BF = false>
 __global__ __launch_bounds__(NT) void rmsnorm_kernel(            // (parameter order: the 14 dwords in front of the first requests first - quant.hip)
     const uint16_t* __restrict__ x, const uint16_t* __restrict__ w, const uint32_t* __restrict__ col_mask, const int32_t* __restrict__ n_dev,
     const int32_t* __restrict__ ind, int ldx, int K, int n_cap, float eps,
@@ -93,7 +112,7 @@ __global__ __launch_bounds__(NT) void rmsnorm_kernel(            // (parameter o
             const uint32_t d[4] = {keep[i].x, keep[i].y, keep[i].z, keep[i].w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float lo = h2f(static_cast<uint16_t>(d[e] & 0xffffu)), hi = h2f(static_cast<uint16_t>(d[e] >> 16));
+                const float lo = a2f<BF>(static_cast<uint16_t>(d[e] & 0xffffu)), hi = a2f<BF>(static_cast<uint16_t>(d[e] >> 16));
                 ss = __fmaf_rn(lo, lo, ss);
                 ss = __fmaf_rn(hi, hi, ss);
             }
@@ -119,7 +138,7 @@ __global__ __launch_bounds__(NT) void rmsnorm_kernel(            // (parameter o
             __syncthreads();
             for (int j = tid; j < n; j += NT) {
                 const int c = ind[j];
-                const uint16_t yv = norm1(xr[c], inv, w[c]);
+                const uint16_t yv = norm1<BF>(xr[c], inv, w[c]);
                 if (x_out) x_out[static_cast<size_t>(row) * ldxo + j] = yv;
                 atomicOr(&smem[c >> 5], 1u << (c & 31));
             }
@@ -139,8 +158,8 @@ __global__ __launch_bounds__(NT) void rmsnorm_kernel(            // (parameter o
             uint32_t y[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                uint32_t lo = norm1(static_cast<uint16_t>(d[e] & 0xffffu), inv, static_cast<uint16_t>(g[e] & 0xffffu));
-                uint32_t hi = norm1(static_cast<uint16_t>(d[e] >> 16), inv, static_cast<uint16_t>(g[e] >> 16));
+                uint32_t lo = norm1<BF>(static_cast<uint16_t>(d[e] & 0xffffu), inv, static_cast<uint16_t>(g[e] & 0xffffu));
+                uint32_t hi = norm1<BF>(static_cast<uint16_t>(d[e] >> 16), inv, static_cast<uint16_t>(g[e] >> 16));
                 if (m8 & (1u << (2 * e)))     lo = 0;
                 if (m8 & (1u << (2 * e + 1))) hi = 0;
                 y[e] = lo | (hi << 16);
@@ -158,11 +177,11 @@ __global__ __launch_bounds__(NT) void rmsnorm_kernel(            // (parameter o
     }
     if constexpr (!QUANT) return;
 
-    float amax = h2f(static_cast<uint16_t>((amax_acc & 0xffffu) > (amax_acc >> 16) ? (amax_acc & 0xffffu) : (amax_acc >> 16)));
+    float amax = a2f<BF>(static_cast<uint16_t>((amax_acc & 0xffffu) > (amax_acc >> 16) ? (amax_acc & 0xffffu) : (amax_acc >> 16)));
     amax = block_max(amax, red + 4);                                      // (its barrier also orders the row's LDS image)
     if (kept && x_out) for (int j = tid; j < ldxo; j += NT) x_out[static_cast<size_t>(row) * ldxo + j] = j < n ? rowimg[j == tid ? gi : ind[j]] : static_cast<uint16_t>(0);
     constexpr float QMAX = static_cast<float>((1 << (BIT - 1)) - 1);
-    const uint16_t sh = mixq_row_scale(amax, QMAX);
+    const uint16_t sh = mixq_row_scale<BF>(amax, QMAX);
     const float s = h2f(sh);
     const float rs = mixq_rcp_scale(s);
     if (tid == 0) {
@@ -181,7 +200,7 @@ __global__ __launch_bounds__(NT) void rmsnorm_kernel(            // (parameter o
                 uint32_t lo = 0, hi = 0;
                 if (in) {
                     uint32_t ub[8], code[8];
-                    quant8_exact<4>(keep[i], s, rs, ub);
+                    quant8_exact<4, BF>(keep[i], s, rs, ub);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) code[e] = f6_code_of_int(quant8_int(ub[e]));
                     f6_pack8(code, lo, hi);
@@ -201,7 +220,7 @@ __global__ __launch_bounds__(NT) void rmsnorm_kernel(            // (parameter o
         const int c = tid + i * NT;
         if (c < nchunk) {
             uint32_t ub[8];
-            quant8_exact<BIT>(keep[i], s, rs, ub);
+            quant8_exact<BIT, BF>(keep[i], s, rs, ub);
             if constexpr (BIT == 8) {
                 uint2 o;
                 o.x = quant8_pack4(ub[0], ub[1], ub[2], ub[3]);
@@ -219,7 +238,7 @@ __global__ __launch_bounds__(NT) void rmsnorm_kernel(            // (parameter o
     }
 }
 
-template <int BIT, bool QUANT>
+template <int BIT, bool QUANT, bool BF>
 int launch_norm(const uint16_t* x, int ldx, const uint16_t* w, float eps, uint16_t* out, int ldout, const int32_t* ind, int n,
                 const int32_t* n_dev, uint16_t* x_scale, void* q, uint16_t* x_out, int ldxo, int32_t* flag, int M, int K,
                 float thr, int qfmt, hipStream_t st, const uint32_t* col_mask = nullptr)
@@ -228,7 +247,7 @@ int launch_norm(const uint16_t* x, int ldx, const uint16_t* w, float eps, uint16
     const int nchunk = K >> 3;
     const int rows16 = qfmt ? ((M + 15) & ~15) : 0;
     dim3 g(M), b(NT);
-#define MIXQ_NLAUNCH(NCH) hipLaunchKernelGGL((rmsnorm_kernel<BIT, NCH, QUANT>), g, b, shm, st, x, w, col_mask, n_dev, ind, ldx, K, n, eps, out, ldout, x_scale, q, x_out, ldxo, flag, thr, rows16, qfmt)
+#define MIXQ_NLAUNCH(NCH) hipLaunchKernelGGL((rmsnorm_kernel<BIT, NCH, QUANT, BF>), g, b, shm, st, x, w, col_mask, n_dev, ind, ldx, K, n, eps, out, ldout, x_scale, q, x_out, ldxo, flag, thr, rows16, qfmt)
     if      (nchunk <= 2 * NT)  MIXQ_NLAUNCH(2);
     else if (nchunk <= 4 * NT)  MIXQ_NLAUNCH(4);
     else if (nchunk <= 8 * NT)  MIXQ_NLAUNCH(8);
@@ -242,16 +261,28 @@ inline float fp16_round(float v) { return static_cast<float>(static_cast<_Float1
 
 }  // namespace
 
-extern "C" int mixq_rmsnorm(const uint16_t* x, const uint16_t* weight, uint16_t* out, int M, int K, int ldx, int ldout, float eps,
-                            mixq_stream_t stream)
+template <bool BF>
+static int rmsnorm_plain(const uint16_t* x, const uint16_t* weight, uint16_t* out, int M, int K, int ldx, int ldout, float eps, mixq_stream_t stream)
 {
     if (M < 0 || K <= 0 || (M > 0 && (!x || !weight || !out))) return MIXQ_EINVAL;
     if ((K & 7) || (ldx & 7) || (ldout & 7) || ldx < K || ldout < K) return MIXQ_ESHAPE;
     if (M == 0) return MIXQ_OK;
-    return launch_norm<8, false>(x, ldx, weight, eps, out, ldout, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, M, K,
-                                 0.f, 0, mixq_stream(stream));
+    return launch_norm<8, false, BF>(x, ldx, weight, eps, out, ldout, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, M, K,
+                                     0.f, 0, mixq_stream(stream));
+}
+extern "C" int mixq_rmsnorm(const uint16_t* x, const uint16_t* weight, uint16_t* out, int M, int K, int ldx, int ldout, float eps,
+                            mixq_stream_t stream)
+{
+    return rmsnorm_plain<false>(x, weight, out, M, K, ldx, ldout, eps, stream);
+}
+// x, weight, out: bfloat16 (the contract in this file's header)
+extern "C" int mixq_rmsnorm_bf16(const uint16_t* x, const uint16_t* weight, uint16_t* out, int M, int K, int ldx, int ldout, float eps,
+                                 mixq_stream_t stream)
+{
+    return rmsnorm_plain<true>(x, weight, out, M, K, ldx, ldout, eps, stream);
 }
 
+template <bool BF>
 static int rmsnorm_quant_common(const uint16_t* x, const uint16_t* weight, uint16_t* out, const int32_t* ind, int n,
                                 const int32_t* n_dev, const uint32_t* col_mask, uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag, int M,
                                 int K, int ldx, int ldout, int ldxo, float eps, int bit, float sigma, int qfmt,
@@ -267,12 +298,16 @@ static int rmsnorm_quant_common(const uint16_t* x, const uint16_t* weight, uint1
     const float qmax = static_cast<float>((1 << (bit - 1)) - 1);
     const float thr = fp16_round(fp16_round(sigma) / qmax);
     uint16_t* xo = (n > 0) ? x_out : nullptr;
-    if (K > 30000) col_mask = nullptr;                  // (as mixq_quant_fused_masked: the kept route keeps an fp16 image of the row in LDS, inside the default 64 KB)
+    if (K > 30000) col_mask = nullptr;                  // (as mixq_quant_fused_masked: the kept route keeps a 16-bit image of the row in LDS, inside the default 64 KB)
     if (bit == 8)
-        return launch_norm<8, true>(x, ldx, weight, eps, out, ldout, ind, n, n_dev, x_scale, q, xo, ldxo, flag, M, K, thr, qfmt,
+        return launch_norm<8, true, BF>(x, ldx, weight, eps, out, ldout, ind, n, n_dev, x_scale, q, xo, ldxo, flag, M, K, thr, qfmt,
+                                        mixq_stream(stream), col_mask);
+    return launch_norm<4, true, BF>(x, ldx, weight, eps, out, ldout, ind, n, n_dev, x_scale, q, xo, ldxo, flag, M, K, thr, qfmt,
                                     mixq_stream(stream), col_mask);
-    return launch_norm<4, true>(x, ldx, weight, eps, out, ldout, ind, n, n_dev, x_scale, q, xo, ldxo, flag, M, K, thr, qfmt,
-                                mixq_stream(stream), col_mask);
+}
+// (a kept map that is missing, too short or misaligned: see mixq_quant_fused_masked)
+static bool norm_kept_map_bad(const uint32_t* col_mask, int map_words, int K, int n) {
+    return n > 0 && (!col_mask || map_words < mixq_kept_map_words(K) || (reinterpret_cast<uintptr_t>(col_mask) & 15));
 }
 
 extern "C" int mixq_rmsnorm_quant_fused(const uint16_t* x, const uint16_t* weight, uint16_t* out, const int32_t* ind, int n,
@@ -280,7 +315,14 @@ extern "C" int mixq_rmsnorm_quant_fused(const uint16_t* x, const uint16_t* weigh
                                         int K, int ldx, int ldout, int ldxo, float eps, int bit, float sigma, int qfmt,
                                         mixq_stream_t stream)
 {
-    return rmsnorm_quant_common(x, weight, out, ind, n, n_dev, nullptr, x_scale, q, x_out, flag, M, K, ldx, ldout, ldxo, eps, bit, sigma, qfmt, stream);
+    return rmsnorm_quant_common<false>(x, weight, out, ind, n, n_dev, nullptr, x_scale, q, x_out, flag, M, K, ldx, ldout, ldxo, eps, bit, sigma, qfmt, stream);
+}
+extern "C" int mixq_rmsnorm_quant_fused_bf16(const uint16_t* x, const uint16_t* weight, uint16_t* out, const int32_t* ind, int n,
+                                             const int32_t* n_dev, uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag, int M,
+                                             int K, int ldx, int ldout, int ldxo, float eps, int bit, float sigma, int qfmt,
+                                             mixq_stream_t stream)
+{
+    return rmsnorm_quant_common<true>(x, weight, out, ind, n, n_dev, nullptr, x_scale, q, x_out, flag, M, K, ldx, ldout, ldxo, eps, bit, sigma, qfmt, stream);
 }
 // ... for a next layer whose prediction is frozen: its kept outlier map (as mixq_quant_fused_masked)
 extern "C" int mixq_rmsnorm_quant_fused_masked(const uint16_t* x, const uint16_t* weight, uint16_t* out, const int32_t* ind, int n,
@@ -288,7 +330,16 @@ extern "C" int mixq_rmsnorm_quant_fused_masked(const uint16_t* x, const uint16_t
                                                int32_t* flag, int M, int K, int ldx, int ldout, int ldxo, float eps, int bit, float sigma,
                                                int qfmt, mixq_stream_t stream)
 {
-    if (n > 0 && (!col_mask || map_words < mixq_kept_map_words(K) || (reinterpret_cast<uintptr_t>(col_mask) & 15))) return MIXQ_EINVAL;   // (see mixq_quant_fused_masked)
-    return rmsnorm_quant_common(x, weight, out, ind, n, n_dev, n > 0 ? col_mask : nullptr, x_scale, q, x_out, flag, M, K, ldx, ldout, ldxo, eps, bit,
-                                sigma, qfmt, stream);
+    if (norm_kept_map_bad(col_mask, map_words, K, n)) return MIXQ_EINVAL;
+    return rmsnorm_quant_common<false>(x, weight, out, ind, n, n_dev, n > 0 ? col_mask : nullptr, x_scale, q, x_out, flag, M, K, ldx, ldout, ldxo, eps, bit,
+                                       sigma, qfmt, stream);
+}
+extern "C" int mixq_rmsnorm_quant_fused_masked_bf16(const uint16_t* x, const uint16_t* weight, uint16_t* out, const int32_t* ind, int n,
+                                                    const int32_t* n_dev, const uint32_t* col_mask, int map_words, uint16_t* x_scale, void* q, uint16_t* x_out,
+                                                    int32_t* flag, int M, int K, int ldx, int ldout, int ldxo, float eps, int bit, float sigma,
+                                                    int qfmt, mixq_stream_t stream)
+{
+    if (norm_kept_map_bad(col_mask, map_words, K, n)) return MIXQ_EINVAL;
+    return rmsnorm_quant_common<true>(x, weight, out, ind, n, n_dev, n > 0 ? col_mask : nullptr, x_scale, q, x_out, flag, M, K, ldx, ldout, ldxo, eps, bit,
+                                      sigma, qfmt, stream);
 }

@@ -35,30 +35,63 @@ def split_pair_rows(joint: torch.Tensor):
     return v[:, 0].reshape(N2 // 2, *rest), v[:, 1].reshape(N2 // 2, *rest)
 
 
+def _is_bf16(config):
+    return getattr(config, "act_dtype", torch.float16) == torch.bfloat16
+
+
 def _refuse_bf16(config, who):
-    """The fused RMSNorm and MixLlamaMLP's fused routes exist in float16 only: under a bfloat16 model (MixqConfig.act_dtype) they say so
-    instead of detouring through float16."""
-    if getattr(config, "act_dtype", torch.float16) == torch.bfloat16:
+    """Under a bfloat16 model (MixqConfig.act_dtype) the fused RMSNorm and MixLlamaMLP serve only a config that opts in with
+    `fused_bf16=True` (config.py: the default refusal is pinned behaviour of this ABI minor); without it they say so instead of detouring
+    through float16.  The joint gate / up launch stays float16 only either way."""
+    if _is_bf16(config) and not getattr(config, "fused_bf16", False):
         raise NotImplementedError(f"{who} has no bfloat16 form yet (the fused RMSNorm, the joint gate / up launch and MixLlamaMLP's fused "
                                   f"routes are float16 only); under act_dtype=torch.bfloat16 call the MixLinear_GEMM layers themselves")
 
 
 class FasterTransformerRMSNorm(nn.Module):
+    """The weight is kept in the model's activation dtype: float16, or bfloat16 when the cache's config says so at construction
+    (MixqConfig(act_dtype=torch.bfloat16, fused_bf16=True)) - the checkpoint's bfloat16 weight then reaches the kernel unrounded.  A module
+    built WITHOUT a cache learns the model's dtype only at forward, from its next layer: it has stored float16 by then, and the bfloat16
+    operand is derived ONCE from that stored weight (RNE_bf16 of the float16 value: a second rounding of a weight that came from a bfloat16
+    checkpoint through float16 is exact only for values float16 holds exactly - hand the cache to the constructor to avoid it)."""
+
     def __init__(self, weight, eps=1e-6, cache=None):
         super().__init__()
-        self.weight = weight.to(torch.float16)
+        config = getattr(cache, "config", None)
+        _refuse_bf16(config, "FasterTransformerRMSNorm")     # (known here when the cache carries the model's config)
+        self.weight = weight.to(torch.bfloat16 if _is_bf16(config) else torch.float16)
         self.variance_epsilon = eps
         self.cache = cache
         self.next_layer = None
-        _refuse_bf16(getattr(cache, "config", None), "FasterTransformerRMSNorm")     # (known here when the cache carries the model's config)
+        object.__setattr__(self, "_weight_bf16", None)       # (weight tensor, its version, the derived bfloat16 operand): see _operand
+
+    def _operand(self, dtype):
+        """`weight` in the model's dtype: the stored tensor itself, or - a module built without a cache under a bfloat16 model - its
+        bfloat16 image, derived once per (weight tensor, version)."""
+        w = self.weight
+        if w.dtype == dtype:
+            return w
+        if dtype != torch.bfloat16:
+            raise RuntimeError(f"FasterTransformerRMSNorm: the weight is {w.dtype}, the model runs in {dtype}")
+        kept = self._weight_bf16
+        if kept is None or kept[0] is not w or kept[1] != w._version:
+            kept = (w, w._version, w.to(torch.bfloat16))
+            object.__setattr__(self, "_weight_bf16", kept)
+        return kept[2]
 
     @torch.no_grad()
     def forward(self, x):
         nl = self.next_layer
-        _refuse_bf16(getattr(nl, "config", None) or getattr(self.cache, "config", None), "FasterTransformerRMSNorm")
+        config = getattr(nl, "config", None) or getattr(self.cache, "config", None)
+        _refuse_bf16(config, "FasterTransformerRMSNorm")
+        dtype = torch.bfloat16 if _is_bf16(config) else torch.float16
+        if x.dtype != dtype:
+            raise RuntimeError(f"FasterTransformerRMSNorm: x must be {str(dtype).replace('torch.', '')} like the model's activations "
+                               f"(MixqConfig.act_dtype), got {x.dtype}")
+        weight = self._operand(dtype)
         output = torch.empty_like(x)
         if nl is None:
-            _backend.layernorm_forward_cuda(x, self.weight, output, self.variance_epsilon)
+            _backend.layernorm_forward_cuda(x, weight, output, self.variance_epsilon)
             return output
         if nl.bit not in (4, 8):
             raise NotImplementedError
@@ -72,7 +105,7 @@ class FasterTransformerRMSNorm(nn.Module):
         ind, n_dev = nl._ind_dev() if (n and ours) else ((nl.ind if n else None), None)
         # (a next layer whose prediction is frozen hands over its kept outlier map: no mask build in front of the row maximum)
         cm = nl._col_mask() if (ours and n and nl.config.norm_kept_map and not nl.add_outliers) else None
-        q, xo = _backend.RMSNormQuantFused(x, self.weight, output, self.variance_epsilon, ind, cache.x_scale, nl.bit,
+        q, xo = _backend.RMSNormQuantFused(x, weight, output, self.variance_epsilon, ind, cache.x_scale, nl.bit,
                                            sigma=getattr(cache, "sigma_value", 6.0), fmt=fmt, n_dev=n_dev, col_mask=cm)
         cache.q_xcache = q
         cache.activation_outliers = xo[:, :n] if n else None
@@ -126,6 +159,8 @@ class MixLlamaMLP(nn.Module):
         up, gate = self.up_proj_, self.gate_proj_
         if not self.config.joint_gate_up or not _backend.PAIR_LAUNCH:
             return False
+        if _is_bf16(self.config):
+            return False                                     # (MIXQ_ACT_SILU_PAIR has no bfloat16 form: the two launches below)
         if up.bit != gate.bit or up.weight_only or gate.weight_only or up.add_outliers:
             return False
         # the kernels with the paired epilogue: int8 on fragment-order weights, int4 as FP6 codes (the default image of either width)

@@ -964,21 +964,36 @@ class ForwardPlan:
 # ------------------------------------------------------------------------------------------------------------
 # RMSNorm in front of the path (mixquant/modules/fused/norm.py:21-33)
 # ------------------------------------------------------------------------------------------------------------
+def _check_norm_dtypes(x, who, **tensors):
+    """The norm's 16-bit tensors share x's container (float16 or bfloat16): no mixing, no silent conversion."""
+    for name, t in tensors.items():
+        if t.dtype != x.dtype:
+            raise RuntimeError(f"{who}: {name} must be {x.dtype} like x, got {t.dtype}")
+
+
 def layernorm_forward_cuda(x, weight, out, eps):
-    """mixlib.layernorm_forward_cuda(x, weight, out, eps): out = RMSNorm(x) * weight (FasterTransformer form)."""
+    """mixlib.layernorm_forward_cuda(x, weight, out, eps): out = RMSNorm(x) * weight (FasterTransformer form).  x float16 or bfloat16
+    (mixq_rmsnorm_bf16); weight and out in x's dtype."""
     _dev_check(x, weight, out)
+    sfx = _act_suffix(x, "layernorm_forward_cuda")
+    _check_norm_dtypes(x, "layernorm_forward_cuda", weight=weight, out=out)
     K = x.shape[-1]
     x2, o2 = x.reshape(-1, K), out.reshape(-1, K)
     xp, ldx = _rows(x2, "x")
     op, ldo = _rows(o2, "out")
-    _capi.call("mixq_rmsnorm", xp, weight.data_ptr(), op, x2.shape[0], K, ldx, ldo, float(eps), _stream())
+    _capi.call("mixq_rmsnorm" + sfx, xp, weight.data_ptr(), op, x2.shape[0], K, ldx, ldo, float(eps), _stream())
     return out
 
 
 def RMSNormQuantFused(x, weight, out, eps, ind, x_scale, bit, sigma=6.0, flag=None, packed=False, fmt=None, n_dev=None, col_mask=None):
     """RMSNorm fused with the next linear's extract + zero + scale + quantise.  Returns (q_x, x_out_view[M,n]); q_x carries
-    its format tag.  `col_mask`: the next layer's kept outlier map of `ind` (as QuantFused)."""
+    its format tag.  `col_mask`: the next layer's kept outlier map of `ind` (as QuantFused).  A bfloat16 x runs the `_bf16` twins: weight
+    and out must be bfloat16 too, x_out is bfloat16, x_scale stays float16."""
     _dev_check(x, weight, out, x_scale, ind, col_mask)
+    sfx = _act_suffix(x, "RMSNormQuantFused")
+    _check_norm_dtypes(x, "RMSNormQuantFused", weight=weight, out=out)
+    if sfx and x_scale.dtype != torch.float16:
+        raise RuntimeError(f"RMSNormQuantFused: x_scale stays float16 under a bfloat16 x, got {x_scale.dtype}")
     fmt = _want_fmt(packed, fmt)
     K = x.shape[-1]
     x2, o2 = x.reshape(-1, K), out.reshape(-1, K)
@@ -992,16 +1007,16 @@ def RMSNormQuantFused(x, weight, out, eps, ind, x_scale, bit, sigma=6.0, flag=No
                     dtype=torch.int8 if bit == 8 else torch.uint8, device=x.device)
     if n:
         ind = _check_ind(ind, "RMSNormQuantFused")
-        x_out = torch.empty((M, (n + 15) // 16 * 16), dtype=torch.float16, device=x.device)
+        x_out = torch.empty((M, (n + 15) // 16 * 16), dtype=x.dtype, device=x.device)
         xop, ldxo, ip = x_out.data_ptr(), x_out.stride(0), ind.data_ptr()
     else:
         x_out, xop, ldxo, ip = None, None, 0, None
     if col_mask is not None and n:
         _check_kept_map(col_mask, K, "RMSNormQuantFused")
-        _capi.call("mixq_rmsnorm_quant_fused_masked", xp, weight.data_ptr(), op, ip, n, _ptr(n_dev), col_mask.data_ptr(), col_mask.numel(), x_scale.data_ptr(),
+        _capi.call("mixq_rmsnorm_quant_fused_masked" + sfx, xp, weight.data_ptr(), op, ip, n, _ptr(n_dev), col_mask.data_ptr(), col_mask.numel(), x_scale.data_ptr(),
                    q.data_ptr(), xop, _ptr(flag), M, K, ldx, ldo, ldxo, float(eps), bit, float(sigma), fmt, _stream())
     else:
-        _capi.call("mixq_rmsnorm_quant_fused", xp, weight.data_ptr(), op, ip, n, _ptr(n_dev), x_scale.data_ptr(), q.data_ptr(), xop,
+        _capi.call("mixq_rmsnorm_quant_fused" + sfx, xp, weight.data_ptr(), op, ip, n, _ptr(n_dev), x_scale.data_ptr(), q.data_ptr(), xop,
                    _ptr(flag), M, K, ldx, ldo, ldxo, float(eps), bit, float(sigma), fmt, _stream())
     return set_fmt(q, fmt), (x_out[:, :n] if n else None)
 
@@ -1010,7 +1025,7 @@ def layernorm_forward_cuda_extract_outliers(x, weight, out, eps, ind, x_scale):
     """mixlib.layernorm_forward_cuda_extract_outliers(x, w, out, eps, ind, x_scale) -> (X_out, q_x) (norm.py:25-28)."""
     q, xo = RMSNormQuantFused(x, weight, out, eps, ind, x_scale, 8)
     if xo is None:
-        xo = torch.empty((q.shape[0], 0), dtype=torch.float16, device=x.device)
+        xo = torch.empty((q.shape[0], 0), dtype=x.dtype, device=x.device)
     return xo, q
 
 
@@ -1018,7 +1033,7 @@ def layernorm_forward_cuda_extract_outliers_int4(x, weight, out, eps, ind, x_sca
     """mixlib.layernorm_forward_cuda_extract_outliers_int4 (norm.py:30-33)."""
     q, xo = RMSNormQuantFused(x, weight, out, eps, ind, x_scale, 4)
     if xo is None:
-        xo = torch.empty((q.shape[0], 0), dtype=torch.float16, device=x.device)
+        xo = torch.empty((q.shape[0], 0), dtype=x.dtype, device=x.device)
     return xo, q
 
 

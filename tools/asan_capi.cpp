@@ -4,7 +4,9 @@
 // the plan / workspace / per-device tables, launch-geometry arithmetic) for out-of-bounds accesses or use-after-free.
 // What it walks: identification, every quantise / detect / dequant / re-tile entry point incl. empty inputs and rejected arguments, the
 // kept-outlier-map routes, the fused GEMMs on every operand layout, mixq_linear_forward on a KEPT argument block (re-used, then edited),
-// the RMSNorm entry points, the W8A16 pair and its addend form - each followed by a device synchronise, results cross-checked where a second route exists.
+// the RMSNorm entry points (the bfloat16 ones on their refusal and M == 0 paths, which need no device: that part also runs on a machine
+// without a GPU, where the driver then stops), the W8A16 pair and its addend form - each followed by a device synchronise, results
+// cross-checked where a second route exists.
 //   build + run: tools/asan_capi.sh (on the GPU box)            exit code 0 and no ASAN report = clean
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -44,7 +46,57 @@ static std::vector<uint32_t> kept_map(const std::vector<int32_t>& ind, int n, in
     return m;
 }
 
+// The bfloat16 RMSNorm entry points on the paths that end before any launch (refusals, M == 0): host code only, so this part also runs
+// on a machine without a GPU.  The pointers are never dereferenced.
+static void norm_bf16_host_paths() {
+    uint16_t* p = reinterpret_cast<uint16_t*>(uintptr_t(4096));
+    int32_t* pi = reinterpret_cast<int32_t*>(uintptr_t(4096));
+    uint32_t* pm = reinterpret_cast<uint32_t*>(uintptr_t(4096));
+    uint32_t* pm_odd = reinterpret_cast<uint32_t*>(uintptr_t(4096 + 8));
+    const int K = 128, words = mixq_kept_map_words(K);
+    CHECK(mixq_rmsnorm_bf16(nullptr, p, p, 4, K, K, K, 1e-5f, nullptr) == MIXQ_EINVAL);
+    CHECK(mixq_rmsnorm_bf16(p, nullptr, p, 4, K, K, K, 1e-5f, nullptr) == MIXQ_EINVAL);
+    CHECK(mixq_rmsnorm_bf16(p, p, nullptr, 4, K, K, K, 1e-5f, nullptr) == MIXQ_EINVAL);
+    CHECK(mixq_rmsnorm_bf16(p, p, p, 4, 132, 136, 136, 1e-5f, nullptr) == MIXQ_ESHAPE);           // K % 8
+    CHECK(mixq_rmsnorm_bf16(p, p, p, 4, K, K, K - 8, 1e-5f, nullptr) == MIXQ_ESHAPE);             // ldout < K
+    CHECK(mixq_rmsnorm_bf16(p, p, p, 4, 32776, 32776, 32776, 1e-5f, nullptr) == MIXQ_ESHAPE);     // more than 16 chunks per thread
+    CHECK(mixq_rmsnorm_bf16(p, p, p, 0, K, K, K, 1e-5f, nullptr) == MIXQ_OK);
+    CHECK(mixq_rmsnorm_bf16(nullptr, nullptr, nullptr, 0, K, K, K, 1e-5f, nullptr) == MIXQ_OK);   // empty inputs may carry null pointers
+    for (int masked = 0; masked < 2; ++masked) {
+        auto f = [&](const uint16_t* x, void* q, const int32_t* ind, int n, uint16_t* xo, int ldxo, int M, int Kv, int bit, int fmt, const uint32_t* map, int mw) {
+            return masked ? mixq_rmsnorm_quant_fused_masked_bf16(x, p, p, ind, n, nullptr, map, mw, p, q, xo, nullptr, M, Kv, Kv, Kv, ldxo, 1e-5f, bit, 6.f, fmt, nullptr)
+                          : mixq_rmsnorm_quant_fused_bf16(x, p, p, ind, n, nullptr, p, q, xo, nullptr, M, Kv, Kv, Kv, ldxo, 1e-5f, bit, 6.f, fmt, nullptr);
+        };
+        CHECK(f(nullptr, p, nullptr, 0, nullptr, 0, 4, K, 8, MIXQ_FMT_PLAIN, nullptr, 0) == MIXQ_EINVAL);
+        CHECK(f(p, nullptr, nullptr, 0, nullptr, 0, 4, K, 8, MIXQ_FMT_PLAIN, nullptr, 0) == MIXQ_EINVAL);
+        CHECK(f(p, p, nullptr, 0, nullptr, 0, 4, K, 5, MIXQ_FMT_PLAIN, nullptr, 0) == MIXQ_EINVAL);              // bit
+        CHECK(f(p, p, nullptr, 0, nullptr, 0, 4, K, 8, MIXQ_FMT_F6X128, nullptr, 0) == MIXQ_EINVAL);             // FP6 codes are 4-bit
+        CHECK(f(p, p, nullptr, 0, nullptr, 0, 4, 132, 8, MIXQ_FMT_PLAIN, nullptr, 0) == MIXQ_ESHAPE);            // K % 8
+        CHECK(f(p, p, nullptr, 0, nullptr, 0, 4, 96, 8, MIXQ_FMT_P16X64, nullptr, 0) == MIXQ_ESHAPE);            // packed: K % 64
+        CHECK(f(p, p, nullptr, 0, nullptr, 0, 4, 192, 4, MIXQ_FMT_R6X128, nullptr, 0) == MIXQ_ESHAPE);           // 4-bit packed: K / 2 % 64
+        CHECK(f(p, p, nullptr, 0, nullptr, 0, 4, 32776, 8, MIXQ_FMT_PLAIN, nullptr, 0) == MIXQ_ESHAPE);
+        CHECK(f(p, p, pi, 3, nullptr, 16, 4, K, 8, MIXQ_FMT_PLAIN, pm, words) == MIXQ_EINVAL);                   // n > 0 needs x_out
+        CHECK(f(p, p, pi, 3, p, 2, 4, K, 8, MIXQ_FMT_PLAIN, pm, words) == MIXQ_EINVAL);                          // ldxo < n
+        if (masked) {
+            CHECK(f(p, p, pi, 3, p, 16, 4, K, 8, MIXQ_FMT_PLAIN, nullptr, words) == MIXQ_EINVAL);                // no map
+            CHECK(f(p, p, pi, 3, p, 16, 4, K, 8, MIXQ_FMT_PLAIN, pm, words - 1) == MIXQ_EINVAL);                 // a shorter layout
+            CHECK(f(p, p, pi, 3, p, 16, 4, K, 8, MIXQ_FMT_PLAIN, pm_odd, words) == MIXQ_EINVAL);                 // not 16-byte aligned
+        }
+        CHECK(f(p, p, pi, 3, p, 16, 0, K, 8, MIXQ_FMT_P16X64, pm, words) == MIXQ_OK);                            // M == 0: every check, no launch
+        CHECK(f(p, p, nullptr, 0, nullptr, 0, 0, 256, 4, MIXQ_FMT_F6X128, nullptr, 0) == MIXQ_OK);
+        CHECK(f(nullptr, nullptr, nullptr, 0, nullptr, 0, 0, K, 8, MIXQ_FMT_PLAIN, nullptr, 0) == MIXQ_OK);
+    }
+}
+
 int main() {
+    CHECK(mixq_version() > 0);
+    norm_bf16_host_paths();
+    int ngpu = 0;
+    if (hipGetDeviceCount(&ngpu) != hipSuccess || ngpu == 0) {                  // (the rest needs device memory)
+        (void)hipGetLastError();
+        printf(g_fail ? "asan_capi: no GPU, host-only part: %d check(s) FAILED\n" : "asan_capi: no GPU, host-only part: all checks passed\n", g_fail);
+        return g_fail ? 1 : 0;
+    }
     char info[64];
     CHECK(mixq_version() > 0);
     CHECK(mixq_device_info(info, 8) == MIXQ_OK && strlen(info) < 8);          // (truncated, terminated)

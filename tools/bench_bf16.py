@@ -4,9 +4,15 @@ forwards on pristine inputs, conditioned_replay: settle, then the median of back
 --rounds rounds so that both see the same box and the same clock history.  Default: the metric shape, 512 x 4096 -> 11008 with 41 outlier
 columns.  Prints one JSON line: per dtype the us per forward of every round, their median and spread.
 
-    python3 tools/bench_bf16.py [--bit 8|4] [--rounds 5] [--steps 20] [--once bf16]
+    python3 tools/bench_bf16.py [--bit 8|4] [--rounds 5] [--steps 20] [--once bf16] [--block]
 
---once DTYPE: build that layer, replay its graph for a profiler (rocprofv3 --kernel-trace --stats -- python3 tools/bench_bf16.py --once bf16)."""
+--once DTYPE: build that layer, replay its graph for a profiler (rocprofv3 --kernel-trace --stats -- python3 tools/bench_bf16.py --once bf16).
+--block: what a bfloat16 model gets with MixqConfig(fused_bf16=True), against float16, same protocol and the same alternating rounds:
+  norm_quant   the fused norm + extract + quantise pass alone (mixlib.RMSNormQuantFused with the next layer's kept outlier map) on the
+               metric's batch, 512 x 4096 with 41 kept outlier columns: mixq_rmsnorm_quant_fused_masked against its _bf16 twin
+  block        FasterTransformerRMSNorm -> MixLlamaMLP at 4096 -> 11008 -> 4096, frozen: float16 as the model runs it (the joint gate / up
+               launch), float16 with joint_gate_up=False (the two launches a bfloat16 block runs too), and bfloat16
+One JSON line: per form the us per call of every round, median, min, max."""
 import argparse
 import json
 import os
@@ -59,6 +65,95 @@ def build(dtype, device, rows, bit, steps, side):
     return g, restore, layer, cfg
 
 
+def _capture(fn, steps, side, warm=4):
+    """`steps` calls of fn(i) as one hipGraph on the side stream, after `warm` eager calls there."""
+    with torch.cuda.stream(side):
+        for i in range(warm):
+            fn(i % steps)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=side):
+            for i in range(steps):
+                fn(i)
+        torch.cuda.synchronize()
+    return g
+
+
+def build_norm_quant(dtype, device, rows, bit, steps, side):
+    """The fused norm + extract + quantise pass of a frozen next layer: (graph, restore)."""
+    from mixq_amd.linear import kept_outlier_map
+    cols, base, _ = bench.make_batches(1, rows, device, 0)
+    base = base.to(dtype)
+    ind = cols.to(torch.int32).to(device)
+    cmap = kept_outlier_map(ind, bench.K)
+    torch.manual_seed(3)
+    w = (torch.rand(bench.K) + 0.5).to(dtype).to(device)
+    xs = torch.zeros((rows, 1), dtype=torch.float16, device=device)
+    out = torch.empty_like(base)
+    fmt = _capi.FMT_P16X64 if bit == 8 else _capi.FMT_R6X128
+    g = _capture(lambda i: mixlib.RMSNormQuantFused(base, w, out, 1e-5, ind, xs, bit, fmt=fmt, col_mask=cmap), steps, side)
+    return g, None, int(ind.numel())
+
+
+def build_block(dtype, device, rows, bit, steps, side, joint):
+    """norm -> MixLlamaMLP of bench.py's secondary block figure (up / gate of `bit` bits, an 8-bit down_proj), frozen: (graph, restore)."""
+    from mixq_amd import FasterTransformerRMSNorm, MixLlamaMLP
+    cfg = MixqConfig(act_dtype=dtype, fused_bf16=(dtype == torch.bfloat16), joint_gate_up=joint)
+    cache = MixLibCache(rows, sigma=bench.SIGMA, bit=bit, device=device, config=cfg)
+
+    def make(seed, k, n, b, name):
+        torch.manual_seed(seed)
+        kw = {}
+        if b == 4:
+            scales = torch.ones(k) + torch.arange(k) * 1e-6
+            cols = bench.outlier_columns(k)
+            scales[cols] = 20.0 + torch.arange(cols.numel()) * 1e-3
+            kw["layer_scales"] = scales
+        return MixLinear_GEMM.from_linear(torch.nn.Linear(k, n, bias=False).to(dtype), b, cache=cache, dev=device, name=name, **kw)
+    up, gate, down = make(21, bench.K, bench.N, bit, "up_proj"), make(22, bench.K, bench.N, bit, "gate_proj"), make(23, bench.N, bench.K, 8, "down_proj")
+    torch.manual_seed(3)
+    norm = FasterTransformerRMSNorm((torch.rand(bench.K) + 0.5).to(dtype).to(device), 1e-5, cache)
+    norm.next_layer = up
+    block = MixLlamaMLP(gate, down, up, cache)
+    _, base, _ = bench.make_batches(1, rows, device, 0)
+    base = base.to(dtype)
+    bx = base.unsqueeze(0).repeat(steps, 1, 1).contiguous()
+    for _ in range(4):
+        block(norm(base.clone()))                            # freezes the predictions (and builds the joint image where it applies)
+    torch.cuda.synchronize()
+    assert not up.add_outliers and not down.add_outliers
+    g = _capture(lambda i: block(norm(bx[i])), steps, side)
+    return g, (lambda: bx.copy_(base.unsqueeze(0).expand_as(bx))), int(up.ind.numel()), block._joint is not None, (block, norm)
+
+
+def block_mode(args, device, side):
+    f16, bf = torch.float16, torch.bfloat16
+    forms = {}
+    forms["norm_quant_fp16"] = build_norm_quant(f16, device, args.batch, args.bit, args.steps, side)
+    forms["norm_quant_bf16"] = build_norm_quant(bf, device, args.batch, args.bit, args.steps, side)
+    forms["block_fp16"] = build_block(f16, device, args.batch, args.bit, args.steps, side, True)
+    forms["block_fp16_two_launch"] = build_block(f16, device, args.batch, args.bit, args.steps, side, False)
+    forms["block_bf16"] = build_block(bf, device, args.batch, args.bit, args.steps, side, True)
+    us = {name: [] for name in forms}
+    for _ in range(args.rounds):
+        for name, f in forms.items():
+            ms, _, _ = bench.conditioned_replay(f[0], side, restore=f[1], replays=args.replays)
+            us[name].append(round(ms * 1e3 / args.steps, 3))
+    out = {"what": f"--block: fused norm + quantise ({args.batch} x {bench.K}, {forms['norm_quant_fp16'][2]} kept outlier columns, W{args.bit}) and norm -> MixLlamaMLP "
+                   f"({bench.K} -> {bench.N} -> {bench.K}, up / gate W{args.bit}A{args.bit}, down W8A8, {forms['block_fp16'][2]} outlier columns of up_proj), "
+                   f"hipGraph of {args.steps} calls, median of {args.replays} replays per round, {args.rounds} alternating rounds",
+           "device": _capi.device_info()}
+    for name in forms:
+        v = sorted(us[name])
+        out[name] = {"us_per_call_rounds": us[name], "median_us": bench.median(v), "min_us": v[0], "max_us": v[-1]}
+        if name.startswith("block"):
+            out[name]["joint_gate_up_launch"] = forms[name][3]
+    out["norm_quant_bf16_over_fp16"] = round(out["norm_quant_bf16"]["median_us"] / out["norm_quant_fp16"]["median_us"], 4)
+    out["block_bf16_over_fp16"] = round(out["block_bf16"]["median_us"] / out["block_fp16"]["median_us"], 4)
+    out["block_bf16_over_fp16_two_launch"] = round(out["block_bf16"]["median_us"] / out["block_fp16_two_launch"]["median_us"], 4)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bit", type=int, choices=[8, 4], default=8)
@@ -67,12 +162,15 @@ def main():
     ap.add_argument("--replays", type=int, default=31)
     ap.add_argument("--batch", type=int, default=bench.M)
     ap.add_argument("--once", choices=["fp16", "bf16"], default=None)
+    ap.add_argument("--block", action="store_true", help="time the fused norm + quantise pass and the norm -> MLP block, bf16 against fp16")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_bf16.py needs an MI355X")
     device = torch.device("cuda", 0)
     torch.cuda.set_device(device)
     side = torch.cuda.Stream()
+    if args.block:
+        return block_mode(args, device, side)
     dtypes = {"fp16": torch.float16, "bf16": torch.bfloat16}
     if args.once:
         g, restore, layer, _ = build(dtypes[args.once], device, args.batch, args.bit, args.steps, side)
