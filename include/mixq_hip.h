@@ -145,7 +145,8 @@ int mixq_device_info(char* buf_host, int cap);
  * Served layouts: MIXQ_X_PACKED | MIXQ_W_F16X64 (int8) and MIXQ_XW_F6X128 (4-bit), at every batch size, by the weights-in-registers
  * kernels; plain / P16X64 layouts, nibble-packed int4 and MIXQ_ACT_SILU_PAIR answer MIXQ_ESHAPE.  A configuration forced with
  * mixq_gemm_set_config that has no bf16 form answers MIXQ_EINVAL before any launch.  Not (yet) in bf16: mixq_gemm_w8a16,
- * mixq_gemm_i8 / mixq_dequant, and MIXQ_ACT_SILU_PAIR (the joint gate / up launch stays fp16 only).
+ * mixq_gemm_i8 / mixq_dequant.  MIXQ_ACT_SILU_PAIR stays refused by THESE entry points (pinned behaviour); the joint gate / up launch in
+ * bf16 has entry points of its own (ABI 1.5 below).
  *
  * ---- bf16 RMSNorm (ABI 1.4): mixq_rmsnorm_bf16, mixq_rmsnorm_quant_fused_bf16, mixq_rmsnorm_quant_fused_masked_bf16 ----
  * The argument lists of their fp16 twins ("RMSNorm in front of the path" below); x, weight, out and x_out hold bfloat16, x_scale stays
@@ -160,7 +161,36 @@ int mixq_device_info(char* buf_host, int cap);
  *   another count than the live one, the K <= 30000 limit and the n_dev live count.
  * Supported range: a row whose inlier maximum exceeds 65504 * qmax has no finite fp16 scale (as above); a bf16 row can also hold values
  * whose squares overflow fp32 - rows whose sum of squares is not finite are outside the supported range.
- * mixq_version() still answers 1003: the number is pinned behaviour of the 1.3 suite; probe for the three symbols instead. */
+ * mixq_version() still answers 1003: the number is pinned behaviour of the 1.3 suite; probe for the three symbols instead.
+ *
+ * ---- bf16 joint gate / up launch (ABI 1.5): mixq_gemm_i8_pair_bf16, mixq_gemm_i4_pair_bf16, mixq_gemm_pair_supported_bf16 ----
+ * MIXQ_ACT_SILU_PAIR (see mixq_gemm_i8_fused: gate_proj and up_proj of an MLP block as ONE GEMM over interleaved weight rows) with the
+ * bfloat16 container: x_out, w_out and y bfloat16, x_scale, scale_col and bias fp16.  The argument lists are mixq_gemm_i8_fused's without
+ * `addend`, `lda` and `act` (the form takes no addend and is its own act); the int8 one ends with the optional row-maximum pair of
+ * mixq_gemm_i8_fused_amax.  N counts the interleaved gate / up rows (groups of four: up[2g], up[2g+1], gate[2g], gate[2g+1]; scale_col,
+ * bias and w_out rows likewise), y is bf16 [M, N / 2], ldy >= N / 2.  The same operations as the two-launch route through the `_bf16`
+ * entry points - up_proj's launch, then gate_proj's MIXQ_ACT_SILU_MUL launch on that tensor - hence the same bytes:
+ *   z     = float(acc) * float(sx[m]) * float(sw[n]) + sum_j float(xo[m,j]) * float(wo[n,j])      (tail on v_mfma_f32_16x16x32_bf16)
+ *   up16  = RNE_bf16( z_up + bias_up )
+ *   y     = RNE_bf16( (silu(z_gate) + bias_gate) * float(up16) )
+ * row_amax (int8 only, optional; zero on entry, >= M words): per row the maximum of the bf16 bit patterns y & 0x7fff over the OUTPUT
+ * columns c < N / 2 whose bit c of col_mask (optional) is clear - what mixq_gemm_i8_fused_amax_bf16(MIXQ_ACT_SILU_MUL) leaves; col_mask is
+ * read only beside row_amax.  The FP6 form has no row-maximum output, as in fp16.
+ * Served: MIXQ_X_PACKED | MIXQ_W_F16X64 (mixq_gemm_i8_pair_bf16) and MIXQ_XW_F6X128 (mixq_gemm_i4_pair_bf16), N % 16 == 0, K % 64 == 0
+ * (4-bit: K % 128 == 0), every batch size, one launch (no N split, as in fp16).  Refusals come in the order of the fused entry points'
+ * checks, all before any launch, the earlier one answering where two coincide:
+ *   1 MIXQ_EINVAL  row_amax beside any layout but MIXQ_X_PACKED | MIXQ_W_F16X64; an unknown layout bit; MIXQ_XW_F6X128 at the int8 entry
+ *   2 MIXQ_EINVAL  M < 0, N < 0, K <= 0, n_out < 0
+ *   3 MIXQ_EINVAL  q_x, q_w, x_scale, scale_col or y NULL (when M > 0 and N > 0)
+ *   4 MIXQ_ESHAPE  a layout the form does not serve (plain, P16X64 on either side, nibble-packed int4; as the `_bf16` entry points, the
+ *                  fragment-order flag in an unserved combination is an unserved layout here, not a bad argument), then N % 16
+ *   5 MIXQ_ESHAPE  K % 64 (4-bit: K % 128), ldy % 4, ldy < N / 2; outlier strides below the padded width or not multiples of 8
+ *   6 MIXQ_EINVAL  pointer alignment ("Alignment and strides")
+ *   7 MIXQ_EINVAL  a configuration forced with mixq_gemm_set_config whose tiling has no paired bf16 form (the forms: 128x192, 64x192,
+ *                  64x256 and 32x64 in both widths, 128x256 in int8) - ahead of
+ *   8 MIXQ_OK      M == 0 or N == 0: nothing is launched.
+ * mixq_gemm_pair_supported_bf16(M, N, K, bit, layout): 1 when the entry point of that width (bit 8 or 4) serves the problem with the
+ * automatic choice, else 0.  mixq_version() still answers 1003; probe for the symbols. */
 
 /* ---- (i) per-token absmax + quantise ------------------------------------------------------------------
  * Replaces mixlib.FindRowScale(x, x_scale, M, K, bit) -> q_x   (linear.py:190-193, :221).
@@ -315,6 +345,18 @@ int mixq_gemm_i8_fused_amax_bf16(const int8_t* q_x, const int8_t* q_w, const uin
                                  uint16_t* y, int ldy, int M, int N, int K, int act, int layout,
                                  uint32_t* row_amax, const uint32_t* col_mask, mixq_stream_t stream);
 int mixq_gemm_amax_supported_bf16(int M, int N, int K, int layout);   /* every batch size: the bf16 forms have no small-batch exception */
+/* ABI 1.5 ("bf16 joint gate / up launch" above): MIXQ_ACT_SILU_PAIR in the bfloat16 container; row_amax and col_mask are optional */
+int mixq_gemm_i8_pair_bf16(const int8_t* q_x, const int8_t* q_w, const uint16_t* x_scale,
+                           const uint16_t* scale_col, const uint16_t* x_out, int ldxo,
+                           const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
+                           const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int K, int layout,
+                           uint32_t* row_amax, const uint32_t* col_mask, mixq_stream_t stream);
+int mixq_gemm_i4_pair_bf16(const uint8_t* q_x, const uint8_t* q_w, const uint16_t* x_scale,
+                           const uint16_t* scale_col, const uint16_t* x_out, int ldxo,
+                           const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
+                           const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int K, int layout,
+                           mixq_stream_t stream);
+int mixq_gemm_pair_supported_bf16(int M, int N, int K, int bit, int layout);
 int mixq_quant_known_amax(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev, uint32_t* row_amax,
                           const uint32_t* col_mask, int map_words, uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag,
                           int M, int K, int ldx, int ldo, int bit, float sigma, int qfmt, mixq_stream_t stream);

@@ -105,6 +105,13 @@ BF16_TWINS = ("mixq_rmsnorm", "mixq_rmsnorm_quant_fused", "mixq_rmsnorm_quant_fu
               "mixq_quant_known_amax", "mixq_selftest_quant_exact",
               "mixq_gemm_i8_fused", "mixq_gemm_i4_fused", "mixq_gemm_i8_fused_amax", "mixq_gemm_amax_supported", "mixq_linear_forward")
 SIGNATURES.update({name + "_bf16": SIGNATURES[name] for name in BF16_TWINS})
+# ABI 1.5: the joint gate / up launch in bfloat16 (entry points of their own: the `_bf16` GEMMs keep refusing ACT_SILU_PAIR)
+PAIR_BF16 = ("mixq_gemm_i8_pair_bf16", "mixq_gemm_i4_pair_bf16", "mixq_gemm_pair_supported_bf16")
+SIGNATURES.update({
+    "mixq_gemm_i8_pair_bf16": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "mixq_gemm_i4_pair_bf16": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "mixq_gemm_pair_supported_bf16": [_I, _I, _I, _I, _I],
+})
 RESTYPES = {"mixq_gemm_workspace_bytes": C.c_longlong}
 
 
@@ -158,6 +165,8 @@ def load():
         except AttributeError as e:
             if name in TUNING_ONLY:
                 continue                                   # the product library: no trace stamps, no tile-order knob
+            if name in PAIR_BF16:
+                continue                                   # a library of an earlier ABI minor (mixq_version() does not tell): callers probe, mixlib.FusedLinear says so
             raise MixqBuildError(f"{LIB_PATH} does not export {name}; rebuild it") from e
         fn.argtypes = argtypes
         fn.restype = RESTYPES.get(name, _I)

@@ -43,8 +43,8 @@ class MixqConfig:
     # The model's activation dtype: ONE per model.  A layer takes x of exactly this dtype and returns y in it (torch.float16, the
     # reference's, or torch.bfloat16: DESIGN.md section 2).  x_scale, scale_col, bias, sigma and the weight_cache buffer are float16 in
     # either case; y, x_out / activation_outliers and an addend / multiplier follow this switch.  Served in bfloat16: MixLinear_GEMM
-    # (W8A8 and W4A4) and, behind `fused_bf16` below, FasterTransformerRMSNorm and MixLlamaMLP; not (yet): weight_only layers and the joint
-    # gate / up launch (a bfloat16 MixLlamaMLP runs up_proj's launch, then gate_proj's with the SiLU-and-multiply epilogue).
+    # (W8A8 and W4A4) and, behind `fused_bf16` below, FasterTransformerRMSNorm and MixLlamaMLP (its joint gate / up launch behind
+    # `joint_gate_up_bf16` on top of that); not (yet): weight_only layers.
     act_dtype: torch.dtype = torch.float16
     # Opt-in to the bfloat16 forms of the fused modules (fused.py): with act_dtype=torch.bfloat16 and fused_bf16=True,
     # FasterTransformerRMSNorm runs the bf16 norm + extract + quantise pass (mixq_rmsnorm*_bf16) and MixLlamaMLP the two-launch route with the
@@ -52,6 +52,12 @@ class MixqConfig:
     # under a bfloat16 config (NotImplementedError at construction) is pinned behaviour of this ABI minor; nothing else speaks against it.
     # Without act_dtype=torch.bfloat16 the switch does nothing.  Not part of key(): it selects no GEMM plan and no weight image.
     fused_bf16: bool = False
+    # Opt-in to the joint gate / up launch of a bfloat16 MixLlamaMLP (mixq_gemm_i8_pair_bf16 / mixq_gemm_i4_pair_bf16, ABI 1.5): the same
+    # bytes as the two-launch route from one launch.  It has an effect only with act_dtype=torch.bfloat16, fused_bf16=True and
+    # joint_gate_up=True.  The default is off ONLY because the refusal is pinned behaviour (a bfloat16 block's `_joint_applies` answers False
+    # under the default flags); nothing else speaks against it.  Not part of key(): the joint image's identity already carries act_dtype,
+    # and the switch selects a route, not an image.
+    joint_gate_up_bf16: bool = False
 
     def __post_init__(self):
         if self.act_dtype not in (torch.float16, torch.bfloat16):

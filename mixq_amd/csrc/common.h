@@ -43,6 +43,7 @@ struct MixqFusedProblem {
     int M, N, KB, act;
     uint32_t* row_amax; const uint32_t* amax_mask;     // the row-maximum side output (mixq_gemm_i8_fused_amax), or null
     bool bf16;                                         // x_out, w_out, addend and y are bfloat16 (the _bf16 entry points)
+    bool bf16_pair = false;                            // ... and the call came through a `_pair_bf16` entry point: MIXQ_ACT_SILU_PAIR is served (the `_bf16` ones refuse it)
 };
 
 #define MIXQ_WAVE 64

@@ -889,12 +889,15 @@ struct Route { int status; RouteKind kind; int cfg, n1, cfg2; };
 
 // (a forced configuration, id >= 0, that the bf16 entry points can run: a weights-in-registers tiling with a bf16 form)
 bool forced_has_bf16(int wbit, int forced) { int c = -1; return cfg_family(forced, &c) == ROUTE_WR && mixq_wr_has_bf16(wbit, c); }
+// (... that the `_pair_bf16` entry points can run: a tiling with the paired epilogue's bf16 form)
+bool forced_has_pair_bf16(int wbit, int forced) { int c = -1; return cfg_family(forced, &c) == ROUTE_WR && mixq_wr_has_pair_bf16(wbit, c); }
 
 // THE place where a route is decided: the fused entry points launch what this returns, the queries (mixq_gemm_pick_config_fmt,
 // mixq_gemm_pick_split[_bf16], mixq_gemm_amax_supported[_bf16]) read it with forced = -1.  `layout` is MIXQ_XW_F6X128 or a valid combination
 // of the flag bits (validate_fused), `act` decides the paired epilogue (and keeps the multiplier form off stream-K), `forced` is this device's
 // mixq_gemm_set_config value: -1 automatic, -2 automatic without the N split, else a config id.  bf16 (x_out, w_out, addend and y are
-// bfloat16; scales and bias stay fp16) is served by the weights-in-registers kernels only, at every batch size.  fp16 asks in this order:
+// bfloat16; scales and bias stay fp16) is served by the weights-in-registers kernels only, at every batch size; bf16 with the paired act
+// (reached through the `_pair_bf16` entry points only: validate_fused) picks with the paired cost pick, no N split.  fp16 asks in this order:
 // FP6 codes, the small-batch kernel, fragment-order weights, stream-K, the LDS-staged kernel.
 Route plan_route(int bit, int layout, int M, int N, int KB, int act, bool want_amax, bool bf16, int forced)
 {
@@ -910,6 +913,12 @@ Route plan_route(int bit, int layout, int M, int N, int KB, int act, bool want_a
     if (bf16) {
         const int wbit = f6 ? 6 : 8;
         if (!f6 && !(bit == 8 && layout == (MIXQ_X_PACKED | MIXQ_W_F16X64))) return refuse(MIXQ_ESHAPE);
+        if (pair) {                                              // the joint gate / up launch: one launch, as in fp16
+            if (f6 && want_amax) return refuse(MIXQ_ESHAPE);
+            if (is_forced && !forced_has_pair_bf16(wbit, forced)) return refuse(MIXQ_EINVAL);
+            r.cfg = is_forced ? fc : mixq_wr_pick_pair_bf16(wbit, M, N, KB);
+            return r.cfg < 0 ? refuse(MIXQ_ESHAPE) : r;
+        }
         if (is_forced && !forced_has_bf16(wbit, forced)) return refuse(MIXQ_EINVAL);
         r.cfg = is_forced ? fc : mixq_wr_pick_bf16(wbit, M, N, KB);
         if (r.cfg < 0) return refuse(MIXQ_ESHAPE);               // (no tiling with a bf16 form serves the problem)
@@ -969,9 +978,10 @@ Route plan_route(int bit, int layout, int M, int N, int KB, int act, bool want_a
 
 // Argument checks of the fused entry points, fp16 and bf16 container alike (p.bf16), before any launch.  The ORDER is part of the C ABI's
 // behaviour - where two faults coincide the earlier check answers: 1 layout (bf16 leaves the two F16X64 combination checks to step 5's
-// MIXQ_ESHAPE), 2 sizes, 3 null operands, 4 act and its operands, 5 what the kernels of the container serve (bf16: no paired form, then the
-// two layouts of the weights-in-registers kernels), 6 K / N / ldy shape, 7 lda, 8 outlier strides, 9 pointer alignment, 10 (bf16) a forced
-// configuration without a bf16 form - ahead of the caller's M == 0 || N == 0 early-out, which fp16's forced-configuration answers follow.
+// MIXQ_ESHAPE), 2 sizes, 3 null operands, 4 act and its operands, 5 what the kernels of the container serve (bf16: no paired form except
+// through the `_pair_bf16` entry points - p.bf16_pair - then the two layouts of the weights-in-registers kernels, then the paired form's
+// N % 16), 6 K / N / ldy shape, 7 lda, 8 outlier strides, 9 pointer alignment, 10 (bf16) a forced configuration without the bf16 form asked
+// for - ahead of the caller's M == 0 || N == 0 early-out, which fp16's forced-configuration answers follow.
 int validate_fused(const MixqFusedProblem& p, int K, int layout, int bit, int forced)
 {
     const bool f6 = layout == MIXQ_XW_F6X128;
@@ -985,9 +995,11 @@ int validate_fused(const MixqFusedProblem& p, int K, int layout, int bit, int fo
     if (p.act == MIXQ_ACT_SILU_MUL && !p.addend) return MIXQ_EINVAL;        // the multiplier is mandatory
     const bool pair = p.act == MIXQ_ACT_SILU_PAIR;                          // interleaved gate / up rows: y has N / 2 columns
     if (p.bf16) {
-        if (pair) return MIXQ_ESHAPE;                                       // (the joint gate / up form is fp16 only)
+        if (pair && !p.bf16_pair) return MIXQ_ESHAPE;                       // (the `_bf16` entry points have no joint gate / up form: the `_pair_bf16` ones)
+        if (pair && p.addend) return MIXQ_EINVAL;
         if (!(f6 || (bit == 8 && layout == (MIXQ_X_PACKED | MIXQ_W_F16X64)))) return MIXQ_ESHAPE;
         if (f6 && p.row_amax) return MIXQ_ESHAPE;
+        if (pair && (p.N & 15)) return MIXQ_ESHAPE;
     } else {
         if (pair && p.addend) return MIXQ_EINVAL;
         if (pair && (!((bit == 8 && wf16) || f6) || (p.N & 15))) return MIXQ_ESHAPE;   // (the weights-in-registers kernels: int8 fragment-order weights, or FP6 codes)
@@ -999,7 +1011,7 @@ int validate_fused(const MixqFusedProblem& p, int K, int layout, int bit, int fo
         if (p.ldxo < need || p.ldwo < need || (p.ldxo & 7) || (p.ldwo & 7)) return MIXQ_ESHAPE;
     }
     if (!mixq_fused_pointers_aligned(p.x_out, p.w_out, p.n_out, p.addend, p.bias, p.y)) return MIXQ_EINVAL;
-    if (p.bf16 && forced >= 0 && !forced_has_bf16(f6 ? 6 : 8, forced)) return MIXQ_EINVAL;
+    if (p.bf16 && forced >= 0 && !(pair ? forced_has_pair_bf16(f6 ? 6 : 8, forced) : forced_has_bf16(f6 ? 6 : 8, forced))) return MIXQ_EINVAL;
     return MIXQ_OK;
 }
 
@@ -1085,6 +1097,34 @@ extern "C" int mixq_gemm_i8_fused_amax_bf16(const int8_t* q_x, const int8_t* q_w
     if (!row_amax) return MIXQ_EINVAL;
     return gemm_fused({q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y, ldy, M, N, K, act,
                        row_amax, col_mask, true}, K, layout, 8, stream);
+}
+// ABI 1.5: the joint gate / up launch in bfloat16 (include/mixq_hip.h).  Entry points of their own - the `_bf16` ones above keep answering
+// MIXQ_ESHAPE for MIXQ_ACT_SILU_PAIR - without an act and an addend argument; N counts the interleaved rows, y is [M, N / 2].
+extern "C" int mixq_gemm_i8_pair_bf16(const int8_t* q_x, const int8_t* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
+                                      const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out,
+                                      const int32_t* n_out_dev, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int K,
+                                      int layout, uint32_t* row_amax, const uint32_t* col_mask, mixq_stream_t stream)
+{
+    // (row_amax beside a layout that has no side output: a bad argument, said where fp16's validate_fused looks at the layout - first)
+    if (row_amax && layout != (MIXQ_X_PACKED | MIXQ_W_F16X64)) return MIXQ_EINVAL;
+    return gemm_fused({q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, nullptr, 0, bias, y, ldy, M, N, K,
+                       MIXQ_ACT_SILU_PAIR, row_amax, row_amax ? col_mask : nullptr, true, true}, K, layout, 8, stream);
+}
+extern "C" int mixq_gemm_i4_pair_bf16(const uint8_t* q_x, const uint8_t* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
+                                      const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out,
+                                      const int32_t* n_out_dev, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int K,
+                                      int layout, mixq_stream_t stream)
+{
+    return gemm_fused({q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, nullptr, 0, bias, y, ldy, M, N, K / 2,
+                       MIXQ_ACT_SILU_PAIR, nullptr, nullptr, true, true}, K, layout, 4, stream);
+}
+// 1 when the entry point of that width serves (M, N, K) with this layout on the current device (automatic choice), else 0
+extern "C" int mixq_gemm_pair_supported_bf16(int M, int N, int K, int bit, int layout)
+{
+    if ((bit != 8 && bit != 4) || M <= 0 || N <= 0 || K <= 0 || (N & 15)) return 0;
+    const bool f6 = layout == MIXQ_XW_F6X128;
+    if (bit == 8 ? (layout != (MIXQ_X_PACKED | MIXQ_W_F16X64) || (K % 64)) : (!f6 || (K % 128))) return 0;
+    return plan_route(bit, layout, M, N, bit == 8 ? K : K / 2, MIXQ_ACT_SILU_PAIR, false, true, -1).status == MIXQ_OK ? 1 : 0;
 }
 // (every batch size runs a weights-in-registers tiling in bf16: no small-batch exception)
 extern "C" int mixq_gemm_amax_supported_bf16(int M, int N, int K, int layout)

@@ -10,7 +10,7 @@ const char* mixq_wr_config_name(int c);
 // config for (M, N, KB) or -1 when the data-parallel kernels of gemm.hip should run instead
 int mixq_wr_pick(int bit, int M, int N, int KB);
 // one launch of tiling c over the weight rows [n_begin, n_begin + n_cols) of problem p (only the launch that ends at p.N may hold a partial
-// tile); bit: 8, 4, or 6 (int4 as FP6 codes).  p.bf16 with a tiling without a bf16 form: MIXQ_EINVAL
+// tile); bit: 8, 4, or 6 (int4 as FP6 codes).  p.bf16 with a tiling without a bf16 form (of the paired epilogue, when p.act asks for it): MIXQ_EINVAL
 int mixq_wr_launch(const MixqFusedProblem& p, int c, int bit, unsigned long long* trace, hipStream_t st, int n_begin, int n_cols);
 // the bf16 forms: the tiling for a problem (-1: none), and whether a (forced) configuration has one
 int mixq_wr_pick_bf16(int bit, int M, int N, int KB);   // bit: 8, or 6 (int4 as FP6 codes)
@@ -27,3 +27,7 @@ bool mixq_wr_ksplit_pays(int M, int N, int KB);   // ... and the tile model says
 // whether a (forced) configuration has the paired epilogue
 int mixq_wr_pick_pair(int bit, int M, int N, int KB);   // bit: 8, or 6 (int4 as FP6 codes)
 bool mixq_wr_has_pair(int bit, int c);
+// ... in bfloat16 (the `_pair_bf16` entry points): the pick (-1: none), whether a (forced) configuration has the form, and its launch handle
+int mixq_wr_pick_pair_bf16(int bit, int M, int N, int KB);
+bool mixq_wr_has_pair_bf16(int bit, int c);
+const void* mixq_wr_bf16_pair_kernel(int bit, int c);   // gemm_wreg_bf16_pair.hip

@@ -218,7 +218,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
     static_assert(LOOK >= 1 && LOADS * NEWER < 64, "vmcnt range");
     static_assert(!EPI2 || SC_END <= 160 * 1024, "X ring + tail blocks + panel flags + scales must fit the 160 KiB of LDS");
     static_assert(!PAIR || (EPI2 && (Q == 0 || Q == 3)), "the paired gate / up epilogue exists in the panel form of the int8 and the FP6 tuple-ring kernels");
-    static_assert(!BF || (!PAIR && ABL == 0 && (Q == 0 || Q == 3)), "bf16 forms: the shipped int8 and FP6 tuple-ring loops, no paired epilogue");
+    static_assert(!BF || ((ABL == 0 || PAIR) && (Q == 0 || Q == 3)), "bf16 forms: the shipped int8 and FP6 tuple-ring loops, plain or with the paired epilogue");
 
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     if constexpr (ABLK == 9) { if (a.act != 12345) return; }                      // launch floor of this grid / LDS footprint
@@ -1127,8 +1127,6 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
 
         if constexpr (EPI2) {
             // ---- EPI2: row panels, software-pipelined, copied out by the loader waves (see the note at its declaration) ----------------
-            typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
             constexpr int NB = PJ * WNB;                                         // 16 x 16 blocks of one panel (per wave)
             constexpr int TQ1 = TQ > 0 ? TQ : 1;
             // (the lane's coordinates again, opaque to the compiler: values derived from them at kernel entry - row indices of the scale
@@ -1268,6 +1266,7 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
             // PAIR: the same piece for the joint gate / up launch - physical columns n .. n+3 of a lane are up[c], up[c+1], gate[c], gate[c+1]
             // of output channels c = n / 2, c + 1.  up goes through the fp16 rounding it has as up_proj's output tensor (z + bias -> fp16,
             // linear.py:285), the product is taken in fp32 and rounded once: what MIXQ_ACT_SILU_MUL computes from that tensor.
+            // (BF: both roundings are to bfloat16 - up_proj's output tensor and y are in the container; bias and scales stay fp16.)
             auto finish_pair = [&](auto st_c, int pn, int i) MIXQ_INL {
                 constexpr bool ST = decltype(st_c)::value;
                 const int nloc = wave * WN + i * 16 + lq * 4, n = n0 + nloc, oc = n >> 1;
@@ -1289,11 +1288,11 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
                     const int m = m0 + j * 16 + lm;
                     f32x4 f = fa[j][i];
                     if (has_bias) { f[0] += bv[0]; f[1] += bv[1]; }
-                    const f16x2 uh = __builtin_convertvector(f32x2{f[0], f[1]}, f16x2);
+                    const uint32_t uh = wr_cvt_pk<BF>(f[0], f[1]);
                     float g0 = wr_silu(f[2]), g1 = wr_silu(f[3]);
                     if (has_bias) { g0 += bv[2]; g1 += bv[3]; }
-                    g0 *= static_cast<float>(uh[0]); g1 *= static_cast<float>(uh[1]);
-                    const uint32_t o = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{g0, g1}, f16x2));
+                    g0 *= a2f<BF>(static_cast<uint16_t>(uh & 0xffffu)); g1 *= a2f<BF>(static_cast<uint16_t>(uh >> 16));
+                    const uint32_t o = wr_cvt_pk<BF>(g0, g1);
                     if (has_amax) {
                         typedef unsigned short us2 __attribute__((ext_vector_type(2)));
                         rmax[j] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(us2, rmax[j]), __builtin_bit_cast(us2, o & keep)));
@@ -1679,7 +1678,28 @@ __global__ __launch_bounds__((WR_CW + LOADERS) * 64) void gemm_wreg_kernel(const
 
 constexpr int WR_SMALL = 14;                           // (index of the 32 x 64 small-batch tiling in g_wr below)
 
-#ifdef MIXQ_WR_BF16_TU
+#if defined(MIXQ_WR_BF16_TU) && MIXQ_WR_BF16_TU == 2
+// ---- the bf16 forms of the joint gate / up launch (this file compiled as gemm_wreg_bf16_pair.hip) ------------------------
+// BF = true AND the paired epilogue (ABL = 90): exactly the nine forms the fp16 table has as k8p / k6p, with the template arguments of the
+// same rows of g_wr (whose geometry the launch reads).  A third translation unit, so that neither existing code object gains a kernel or a
+// symbol (see the note at the kernel's template head) and tools/check_wreg_asm.py lists these under their own file name.
+struct WrBf16Pair { int cfg; void (*k8p)(const WrArgs); void (*k6p)(const WrArgs); };
+#define MIXQ_WRBP8(C, MBv, WNBv, NS, Dv, LD) { C, gemm_wreg_kernel<MBv, WNBv, NS, Dv, 0, LD, 90, true>, nullptr }
+#define MIXQ_WRBP(C, MBv, WNBv, NS, Dv, LD, NS6, D6) { C, gemm_wreg_kernel<MBv, WNBv, NS, Dv, 0, LD, 90, true>, gemm_wreg_kernel<MBv, WNBv, NS6, D6, 3, LD, 90, true> }
+const WrBf16Pair g_wr_bf16_pair[] = {
+    MIXQ_WRBP(0, 8, 3, 16, 4, 2, 8, 2), MIXQ_WRBP8(5, 8, 4, 16, 3, 2), MIXQ_WRBP(7, 4, 3, 16, 4, 2, 12, 3), MIXQ_WRBP(8, 4, 4, 16, 4, 2, 12, 3),
+    MIXQ_WRBP(WR_SMALL, 2, 1, 8, 6, 1, 12, 4),
+};
+}  // namespace
+
+// the kernel (launch handle) of tiling c's paired bf16 form, or nullptr: bit 8, or 6 (int4 as FP6 codes); launched by mixq_wr_launch
+const void* mixq_wr_bf16_pair_kernel(int bit, int c)
+{
+    for (const auto& b : g_wr_bf16_pair)
+        if (b.cfg == c) return reinterpret_cast<const void*>(bit == 8 ? b.k8p : (bit == 6 ? b.k6p : nullptr));
+    return nullptr;
+}
+#elif defined(MIXQ_WR_BF16_TU)
 // ---- the bf16 forms (this file compiled as gemm_wreg_bf16.hip) ---------------------------------------------------------
 // BF = true: bf16 x_out / w_out / addend / y.  Only what the automatic choice can return - the tilings of g_cost8 / g_cost6 plus WR_SMALL -
 // with the template arguments of the same rows of g_wr (whose geometry the launch reads).  No nibble form, no paired epilogue, no probes.
@@ -1874,6 +1894,15 @@ int mixq_wr_pick_pair(int bit, int M, int N, int KB)
     return wr_cheapest(bit == 6 ? 6 : 8, M, N, KB, mixq_num_cus(), [bit](int, const WrConfig& g) { return (bit == 6 ? g.k6p : g.k8p) != nullptr; });
 }
 bool mixq_wr_has_pair(int bit, int c) { return c >= 0 && c < NUM_WR && (bit == 6 ? g_wr[c].k6p : g_wr[c].k8p) != nullptr; }
+// ... and in bfloat16 (mixq_gemm_i8_pair_bf16 / mixq_gemm_i4_pair_bf16): the paired cost pick among the tilings gemm_wreg_bf16_pair.hip has
+// the form of; no N split, as in fp16.  -1: none serves the problem
+int mixq_wr_pick_pair_bf16(int bit, int M, int N, int KB)
+{
+    if (bit != 8 && bit != 6) return -1;
+    if (M <= 32) return mixq_wr_bf16_pair_kernel(bit, WR_SMALL) ? WR_SMALL : -1;
+    return wr_cheapest(bit, M, N, KB, mixq_num_cus(), [bit](int c, const WrConfig&) { return mixq_wr_bf16_pair_kernel(bit, c) != nullptr; });
+}
+bool mixq_wr_has_pair_bf16(int bit, int c) { return c >= 0 && c < NUM_WR && mixq_wr_bf16_pair_kernel(bit, c) != nullptr; }
 int mixq_wr_ksplit_config() { return WR_KSPLIT; }
 // Can the pairwise split-K form (WR_KSPLIT) run (M, N, KB) on the current device?  MIXQ_OK, or why not: both halves of every tile must be
 // resident at once (2 x tiles <= CUs), the workspace registered with mixq_gemm_set_workspace must hold a flag word and an int32 slot per tile.
@@ -1938,9 +1967,11 @@ int mixq_wr_launch(const MixqFusedProblem& p, int c, int bit, unsigned long long
 {
     const int M = p.M, N = p.N, KB = p.KB;
     if (c < 0 || c >= NUM_WR) return MIXQ_EINVAL;
-    if (p.bf16 && (p.act == MIXQ_ACT_SILU_PAIR || !mixq_wr_bf16_kernel(bit, c))) return MIXQ_EINVAL;    // (no paired epilogue, no form outside gemm_wreg_bf16.hip's table)
-    if (n_begin < 0 || (n_begin & 63) || n_cols <= 0 || n_begin + n_cols > N) return MIXQ_EINVAL;
     const bool pair = p.act == MIXQ_ACT_SILU_PAIR;                          // (the paired epilogue is a kernel form, not a run-time switch)
+    // the bf16 forms live in code objects of their own: gemm_wreg_bf16.hip's table, and gemm_wreg_bf16_pair.hip's for the paired epilogue
+    const void* kbf = !p.bf16 ? nullptr : (pair ? mixq_wr_bf16_pair_kernel(bit, c) : mixq_wr_bf16_kernel(bit, c));
+    if (p.bf16 && !kbf) return MIXQ_EINVAL;                                 // (no form of this tiling in that table)
+    if (n_begin < 0 || (n_begin & 63) || n_cols <= 0 || n_begin + n_cols > N) return MIXQ_EINVAL;
     if (pair && ((bit != 8 && bit != 6) || (N & 3) || p.addend)) return MIXQ_EINVAL;
     const WrConfig& g = g_wr[c];
     WrArgs a;
@@ -1967,7 +1998,7 @@ int mixq_wr_launch(const MixqFusedProblem& p, int c, int bit, unsigned long long
     a.trace = trace;
     a.row_amax = p.row_amax; a.amax_mask = p.amax_mask;
     void (*k)(const WrArgs) = pair ? (bit == 8 ? g.k8p : g.k6p) : (bit == 8 ? g.k8 : (bit == 6 ? g.k6 : g.k4));
-    const void* kh = p.bf16 ? mixq_wr_bf16_kernel(bit, c) : reinterpret_cast<const void*>(k);     // (the bf16 forms live in gemm_wreg_bf16.hip's code object)
+    const void* kh = p.bf16 ? kbf : reinterpret_cast<const void*>(k);
     if (!kh) return MIXQ_EINVAL;
     int units = a.tiles_m * a.tiles_n;
     if (c == WR_KSPLIT) {

@@ -42,7 +42,7 @@ def _is_bf16(config):
 def _refuse_bf16(config, who):
     """Under a bfloat16 model (MixqConfig.act_dtype) the fused RMSNorm and MixLlamaMLP serve only a config that opts in with
     `fused_bf16=True` (config.py: the default refusal is pinned behaviour of this ABI minor); without it they say so instead of detouring
-    through float16.  The joint gate / up launch stays float16 only either way."""
+    through float16.  (The joint gate / up launch of a bfloat16 block is a further opt-in: `joint_gate_up_bf16`.)"""
     if _is_bf16(config) and not getattr(config, "fused_bf16", False):
         raise NotImplementedError(f"{who} has no bfloat16 form yet (the fused RMSNorm, the joint gate / up launch and MixLlamaMLP's fused "
                                   f"routes are float16 only); under act_dtype=torch.bfloat16 call the MixLinear_GEMM layers themselves")
@@ -159,8 +159,9 @@ class MixLlamaMLP(nn.Module):
         up, gate = self.up_proj_, self.gate_proj_
         if not self.config.joint_gate_up or not _backend.PAIR_LAUNCH:
             return False
-        if _is_bf16(self.config):
-            return False                                     # (MIXQ_ACT_SILU_PAIR has no bfloat16 form: the two launches below)
+        if _is_bf16(self.config) and not (getattr(self.config, "fused_bf16", False) and getattr(self.config, "joint_gate_up_bf16", False)
+                                          and _backend.PAIR_LAUNCH_BF16):
+            return False                                     # (bfloat16: the joint launch is an opt-in of its own, config.py; else the two launches below)
         if up.bit != gate.bit or up.weight_only or gate.weight_only or up.add_outliers:
             return False
         # the kernels with the paired epilogue: int8 on fragment-order weights, int4 as FP6 codes (the default image of either width)
@@ -211,8 +212,10 @@ class MixLlamaMLP(nn.Module):
             bias = interleave_pair_rows(zero if up.bias is None else up.bias, zero if gate.bias is None else gate.bias)
         wo = None
         if n:
-            wo = torch.zeros((2 * N, _L._pad16(n)), dtype=torch.float16, device=scale.device)
-            wo[:, :n] = interleave_pair_rows(up.weight_cache, gate.weight_cache)
+            # (bfloat16: the bf16 IMAGE of the interleaved float16 weight_cache rows - one RNE, as each layer's own `_wo_operand`; rounding is
+            # elementwise, so interleaving first gives the bytes the two layers' images hold)
+            wo = torch.zeros((2 * N, _L._pad16(n)), dtype=self.config.act_dtype, device=scale.device)
+            wo[:, :n] = interleave_pair_rows(up.weight_cache, gate.weight_cache).to(self.config.act_dtype)
             wo = wo[:, :n]
         old = self._joint
         j = {"wpk": wpk, "rows": 2 * N, "scale": scale, "bias": bias, "wo": wo,
@@ -290,13 +293,15 @@ class MixLlamaMLP(nn.Module):
             xo, wo = _L._wide(xo, n_cap), _L._wide(wo, n_cap)
         extra = {}
         target = None
+        # (the container is said only where it is not float16, as MixLinear_GEMM._gemm does: another backend keeps the reference's argument lists)
+        dt = {} if self.config.act_dtype == torch.float16 else {"dtype": self.config.act_dtype}
         if self.config.fuse_down_amax and up.bit == 8 and down.bit == 8 and down.in_features == N and \
-                _backend.amax_supported(M, 2 * N, K, _L.FMT_P16X64, _L.FMT_F16X64):
+                _backend.amax_supported(M, 2 * N, K, _L.FMT_P16X64, _L.FMT_F16X64, **dt):
             target = down.amax_target(M, x.device)
             if target is not None:
                 extra = {"row_amax": target[0], "col_mask": target[1]}
         y = _backend.FusedLinear(cache.q_xcache, j["wpk"], cache.x_scale, j["scale"], xo, wo, n_cap, j["bias"], M, 2 * N, K, bit=up.bit,
-                                 act=_hip_mixlib.ACT_SILU_PAIR, n_out_dev=n_dev, **extra)
+                                 act=_hip_mixlib.ACT_SILU_PAIR, n_out_dev=n_dev, **dt, **extra)
         out = y.reshape(cache.shape)
         if target is not None:
             out._mixq_row_amax = (target[0], down, out._version)

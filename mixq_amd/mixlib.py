@@ -789,6 +789,17 @@ def _aligned_addend(addend):
 
 
 PAIR_LAUNCH = True                       # FusedLinear serves ACT_SILU_PAIR (fused.MixLlamaMLP asks before taking its joint gate / up route)
+PAIR_LAUNCH_BF16 = True                  # ... and with dtype=torch.bfloat16 (ABI 1.5: mixq_gemm_i8_pair_bf16 / mixq_gemm_i4_pair_bf16)
+
+
+def _pair_bf16_entry(name):
+    """An ABI 1.5 entry point of the loaded library.  mixq_version() does not tell 1.5 from 1.3 (the number is pinned), so the symbol itself is
+    probed: a library built before it says so here, by name - nothing falls back to another route."""
+    fn = getattr(_capi.load(), name, None)
+    if fn is None:
+        raise RuntimeError(f"FusedLinear: the loaded library ({_capi.LIB_PATH}) does not export {name} (ABI 1.5, the joint gate / up launch in "
+                           f"bfloat16); rebuild it")
+    return fn
 
 
 def _check_same_dtype(dtype, who, **tensors):
@@ -810,7 +821,8 @@ def amax_supported(M, N, K, x_fmt, w_fmt, dtype=torch.float16):
 def FusedLinear(q_x, q_w, x_scale, scale_col, x_out, w_out, n_out, bias, M, N, K, bit=8, act=ACT_NONE, n_out_dev=None,
                 addend=None, out=None, x_packed=None, w_packed=None, row_amax=None, col_mask=None, dtype=torch.float16):
     """(iii)+(iv): int8/int4 MFMA GEMM + dequant + fp16 outlier correction + addend + act + bias -> fp16 [M,N].
-    `dtype` (float16, or bfloat16: the `_bf16` entry points) is the container of x_out, w_out, addend and y - with no outlier columns, no
+    `dtype` (float16, or bfloat16: the `_bf16` entry points; ACT_SILU_PAIR in bfloat16: the `_pair_bf16` ones, ABI 1.5 - a library without
+    them is a RuntimeError naming the symbol) is the container of x_out, w_out, addend and y - with no outlier columns, no
     addend and no `out` there is no 16-bit tensor to read it from, so it is said; the tensors that are present must agree with it.
     x_scale, scale_col and bias are float16 in either form.
     The operand layouts come from the tensors' own format tags (set_fmt / the packing and quantising functions above);
@@ -828,8 +840,9 @@ def FusedLinear(q_x, q_w, x_scale, scale_col, x_out, w_out, n_out, bias, M, N, K
     if act == ACT_SILU_PAIR and (N % 16 or not _is_zero_addend(addend)):
         raise RuntimeError("FusedLinear: ACT_SILU_PAIR needs N % 16 == 0 and takes no addend")
     sfx = _act_suffix(dtype, "FusedLinear")
-    if sfx and act == ACT_SILU_PAIR:
-        raise RuntimeError("FusedLinear: ACT_SILU_PAIR (the joint gate / up launch) has no bfloat16 form")
+    pair_bf16 = bool(sfx) and act == ACT_SILU_PAIR           # (entry points of their own: no addend, no act argument)
+    if pair_bf16:
+        fn_pair = _pair_bf16_entry("mixq_gemm_i8_pair_bf16" if bit == 8 else "mixq_gemm_i4_pair_bf16")
     y = out if out is not None else torch.empty((M, N // 2 if act == ACT_SILU_PAIR else N), dtype=dtype, device=q_x.device)
     _check_same_dtype(dtype, "FusedLinear", out=out)
     if out is not None:
@@ -859,6 +872,14 @@ def FusedLinear(q_x, q_w, x_scale, scale_col, x_out, w_out, n_out, bias, M, N, K
     if row_amax is not None:
         if bit != 8 or row_amax.numel() < M or row_amax.element_size() != 4:
             raise RuntimeError("FusedLinear: row_amax needs an int8 GEMM and a 4-byte buffer of at least M entries")
+    if pair_bf16:
+        args = (q_x.data_ptr(), q_w.data_ptr(), x_scale.data_ptr(), scale_col.data_ptr(), xop, ldxo, wop, ldwo, n_out, _ptr(n_out_dev),
+                _ptr(bias), y.data_ptr(), y.stride(0), M, N, K, _layout_bits(x_fmt, w_fmt))
+        rc = fn_pair(*args, _ptr(row_amax), _ptr(col_mask), _stream()) if bit == 8 else fn_pair(*args, _stream())
+        if rc != 0:
+            raise _capi.MixqError("mixq_gemm_i8_pair_bf16" if bit == 8 else "mixq_gemm_i4_pair_bf16", rc)
+        return y
+    if row_amax is not None:
         _capi.call("mixq_gemm_i8_fused_amax" + sfx, q_x.data_ptr(), q_w.data_ptr(), x_scale.data_ptr(), scale_col.data_ptr(), xop, ldxo, wop, ldwo,
                    n_out, _ptr(n_out_dev), ap, lda, _ptr(bias), y.data_ptr(), y.stride(0), M, N, K, act, _layout_bits(x_fmt, w_fmt),
                    row_amax.data_ptr(), _ptr(col_mask), _stream())

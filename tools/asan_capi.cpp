@@ -5,7 +5,7 @@
 // What it walks: identification, every quantise / detect / dequant / re-tile entry point incl. empty inputs and rejected arguments, the
 // kept-outlier-map routes, the fused GEMMs on every operand layout, mixq_linear_forward on a KEPT argument block (re-used, then edited),
 // the RMSNorm entry points (the bfloat16 ones on their refusal and M == 0 paths, which need no device: that part also runs on a machine
-// without a GPU, where the driver then stops), the W8A16 pair and its addend form - each followed by a device synchronise, results
+// without a GPU, where the driver then stops; likewise the bfloat16 joint gate / up entry points of ABI 1.5), the W8A16 pair and its addend form - each followed by a device synchronise, results
 // cross-checked where a second route exists.
 //   build + run: tools/asan_capi.sh (on the GPU box)            exit code 0 and no ASAN report = clean
 #include <hip/hip_runtime.h>
@@ -88,9 +88,68 @@ static void norm_bf16_host_paths() {
     }
 }
 
+// The joint gate / up launch in bfloat16 (ABI 1.5) on the paths that end before any launch: every refusal of include/mixq_hip.h's list,
+// M == 0, the query, and a forced tiling with and without the paired bf16 form.  Host code only; the pointers are never dereferenced.
+static void pair_bf16_host_paths() {
+    int8_t* q = reinterpret_cast<int8_t*>(uintptr_t(4096));
+    uint8_t* q4 = reinterpret_cast<uint8_t*>(uintptr_t(4096));
+    uint16_t* p = reinterpret_cast<uint16_t*>(uintptr_t(4096));
+    uint16_t* p8 = reinterpret_cast<uint16_t*>(uintptr_t(4096 + 8));
+    uint32_t* pm = reinterpret_cast<uint32_t*>(uintptr_t(4096));
+    const int wf16 = MIXQ_X_PACKED | MIXQ_W_F16X64, f6 = MIXQ_XW_F6X128, M = 64, N = 128, K = 128;
+    auto i8 = [&](const int8_t* qx, uint16_t* y, int ldy, int Mv, int Nv, int Kv, int layout, uint32_t* amax, const uint16_t* xo = nullptr, int ldo = 0, int n_out = 0) {
+        return mixq_gemm_i8_pair_bf16(qx, q, p, p, xo, ldo, xo, ldo, n_out, nullptr, nullptr, y, ldy, Mv, Nv, Kv, layout, amax, nullptr, nullptr);
+    };
+    auto i4 = [&](const uint8_t* qx, uint16_t* y, int ldy, int Mv, int Nv, int Kv, int layout) {
+        return mixq_gemm_i4_pair_bf16(qx, q4, p, p, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, y, ldy, Mv, Nv, Kv, layout, nullptr);
+    };
+    CHECK(mixq_gemm_set_config(-1) == MIXQ_OK);
+    CHECK(i8(nullptr, p, 64, M, N, K, wf16, nullptr) == MIXQ_EINVAL);
+    CHECK(i8(q, nullptr, 64, M, N, K, wf16, nullptr) == MIXQ_EINVAL);
+    CHECK(i4(nullptr, p, 64, M, N, K, f6) == MIXQ_EINVAL);
+    CHECK(i8(q, p, 64, M, N, K, 64, nullptr) == MIXQ_EINVAL);                                      // an unknown layout bit
+    CHECK(i8(q, p, 64, M, N, K, f6, nullptr) == MIXQ_EINVAL);                                      // FP6 codes are the 4-bit entry's
+    CHECK(i8(q, p, 64, M, N, K, MIXQ_X_PACKED | MIXQ_W_PACKED, pm) == MIXQ_EINVAL);                // row_amax beside a layout without the side output
+    CHECK(i8(q, p, 64, M, N, K, MIXQ_X_PACKED | MIXQ_W_PACKED, nullptr) == MIXQ_ESHAPE);
+    CHECK(i8(q, p, 64, M, N, K, 0, nullptr) == MIXQ_ESHAPE);
+    CHECK(i4(q4, p, 64, M, N, K, wf16) == MIXQ_ESHAPE);
+    CHECK(i4(q4, p, 64, M, N, K, MIXQ_X_PACKED | MIXQ_W_PACKED) == MIXQ_ESHAPE);
+    CHECK(i8(q, p, 64, M, N, 96, wf16, nullptr) == MIXQ_ESHAPE);                                   // K % 64
+    CHECK(i4(q4, p, 64, M, N, 192, f6) == MIXQ_ESHAPE);                                            // 4-bit: K % 128
+    CHECK(i8(q, p, 64, M, 136, K, wf16, nullptr) == MIXQ_ESHAPE);                                  // N % 16
+    CHECK(i8(q, p, 60, M, N, K, wf16, nullptr) == MIXQ_ESHAPE);                                    // ldy < N / 2
+    CHECK(i8(q, p, 64, M, N, K, wf16, nullptr, p, 8, 3) == MIXQ_ESHAPE);                           // outlier stride below the padded width
+    CHECK(i8(q, p8 - 2, 64, M, N, K, wf16, nullptr) == MIXQ_EINVAL);                               // y 4-byte aligned only
+    CHECK(i8(q, p, 64, M, N, K, wf16, nullptr, p8, 16, 3) == MIXQ_EINVAL);                         // x_out / w_out 8-byte aligned only
+    CHECK(i8(q, p, 64, 0, N, K, wf16, pm) == MIXQ_OK);                                             // M == 0: every check, no launch
+    CHECK(i8(nullptr, nullptr, 64, 0, N, K, wf16, nullptr) == MIXQ_OK);
+    CHECK(i4(q4, p, 64, 0, N, K, f6) == MIXQ_OK);
+    CHECK(i8(q, p, 64, 0, N, 96, wf16, nullptr) == MIXQ_ESHAPE);                                   // ... the shape checks included
+    CHECK(mixq_gemm_pair_supported_bf16(M, N, K, 8, wf16) == 1);
+    CHECK(mixq_gemm_pair_supported_bf16(M, N, K, 4, f6) == 1);
+    CHECK(mixq_gemm_pair_supported_bf16(M, N, 96, 8, wf16) == 0);
+    CHECK(mixq_gemm_pair_supported_bf16(M, N, K, 8, MIXQ_X_PACKED | MIXQ_W_PACKED) == 0);
+    CHECK(mixq_gemm_pair_supported_bf16(M, N, K, 4, wf16) == 0);
+    CHECK(mixq_gemm_pair_supported_bf16(M, 136, K, 8, wf16) == 0);
+    CHECK(mixq_gemm_pair_supported_bf16(0, N, K, 8, wf16) == 0);
+    CHECK(mixq_gemm_pair_supported_bf16(M, N, K, 5, wf16) == 0);
+    // forced configurations: every id either has the paired bf16 form (the empty problem is then MIXQ_OK) or is refused ahead of M == 0
+    int with8 = 0, with6 = 0;
+    for (int c = 0; c < mixq_gemm_num_configs(); ++c) {
+        CHECK(mixq_gemm_set_config(c) == MIXQ_OK);
+        const int r8 = i8(q, p, 64, 0, N, K, wf16, nullptr), r6 = i4(q4, p, 64, 0, N, K, f6);
+        CHECK(r8 == MIXQ_OK || r8 == MIXQ_EINVAL);
+        CHECK(r6 == MIXQ_OK || r6 == MIXQ_EINVAL);
+        with8 += r8 == MIXQ_OK; with6 += r6 == MIXQ_OK;
+    }
+    CHECK(mixq_gemm_set_config(-1) == MIXQ_OK);
+    CHECK(with8 == 5 && with6 == 4);
+}
+
 int main() {
     CHECK(mixq_version() > 0);
     norm_bf16_host_paths();
+    pair_bf16_host_paths();
     int ngpu = 0;
     if (hipGetDeviceCount(&ngpu) != hipSuccess || ngpu == 0) {                  // (the rest needs device memory)
         (void)hipGetLastError();

@@ -6,13 +6,16 @@ columns.  Prints one JSON line: per dtype the us per forward of every round, the
 
     python3 tools/bench_bf16.py [--bit 8|4] [--rounds 5] [--steps 20] [--once bf16] [--block]
 
---once DTYPE: build that layer, replay its graph for a profiler (rocprofv3 --kernel-trace --stats -- python3 tools/bench_bf16.py --once bf16).
+--once DTYPE: build that layer, replay its graph for a profiler (rocprofv3 --kernel-trace --stats -- python3 tools/bench_bf16.py --once bf16);
+  --once block_bf16_joint (or any other block form's name): the same for one form of --block.
 --block: what a bfloat16 model gets with MixqConfig(fused_bf16=True), against float16, same protocol and the same alternating rounds:
   norm_quant   the fused norm + extract + quantise pass alone (mixlib.RMSNormQuantFused with the next layer's kept outlier map) on the
                metric's batch, 512 x 4096 with 41 kept outlier columns: mixq_rmsnorm_quant_fused_masked against its _bf16 twin
-  block        FasterTransformerRMSNorm -> MixLlamaMLP at 4096 -> 11008 -> 4096, frozen: float16 as the model runs it (the joint gate / up
-               launch), float16 with joint_gate_up=False (the two launches a bfloat16 block runs too), and bfloat16
-One JSON line: per form the us per call of every round, median, min, max."""
+  block        FasterTransformerRMSNorm -> MixLlamaMLP at 4096 -> 11008 -> 4096, frozen, each dtype with the joint gate / up launch on and
+               off: float16 as the model runs it (joint), float16 with joint_gate_up=False, bfloat16 as a fused_bf16 model runs it (the two
+               launches), and bfloat16 with joint_gate_up_bf16=True (mixq_gemm_i8_pair_bf16 / mixq_gemm_i4_pair_bf16)
+One JSON line: per form the us per call of every round, median, min, max; and what the joint launch saves in either dtype beside the
+spread of the bfloat16 two-launch rounds."""
 import argparse
 import json
 import os
@@ -96,9 +99,11 @@ def build_norm_quant(dtype, device, rows, bit, steps, side):
 
 
 def build_block(dtype, device, rows, bit, steps, side, joint):
-    """norm -> MixLlamaMLP of bench.py's secondary block figure (up / gate of `bit` bits, an 8-bit down_proj), frozen: (graph, restore)."""
+    """norm -> MixLlamaMLP of bench.py's secondary block figure (up / gate of `bit` bits, an 8-bit down_proj), frozen: (graph, restore).
+    joint: the joint gate / up launch - joint_gate_up for float16; bfloat16 keeps that switch on and takes joint_gate_up_bf16."""
     from mixq_amd import FasterTransformerRMSNorm, MixLlamaMLP
-    cfg = MixqConfig(act_dtype=dtype, fused_bf16=(dtype == torch.bfloat16), joint_gate_up=joint)
+    bf = dtype == torch.bfloat16
+    cfg = MixqConfig(act_dtype=dtype, fused_bf16=bf, joint_gate_up=True if bf else joint, joint_gate_up_bf16=bf and joint)
     cache = MixLibCache(rows, sigma=bench.SIGMA, bit=bit, device=device, config=cfg)
 
     def make(seed, k, n, b, name):
@@ -133,7 +138,9 @@ def block_mode(args, device, side):
     forms["norm_quant_bf16"] = build_norm_quant(bf, device, args.batch, args.bit, args.steps, side)
     forms["block_fp16"] = build_block(f16, device, args.batch, args.bit, args.steps, side, True)
     forms["block_fp16_two_launch"] = build_block(f16, device, args.batch, args.bit, args.steps, side, False)
-    forms["block_bf16"] = build_block(bf, device, args.batch, args.bit, args.steps, side, True)
+    forms["block_bf16"] = build_block(bf, device, args.batch, args.bit, args.steps, side, False)
+    forms["block_bf16_joint"] = build_block(bf, device, args.batch, args.bit, args.steps, side, True)
+    assert [forms[n][3] for n in ("block_fp16", "block_fp16_two_launch", "block_bf16", "block_bf16_joint")] == [True, False, False, True]
     us = {name: [] for name in forms}
     for _ in range(args.rounds):
         for name, f in forms.items():
@@ -151,6 +158,11 @@ def block_mode(args, device, side):
     out["norm_quant_bf16_over_fp16"] = round(out["norm_quant_bf16"]["median_us"] / out["norm_quant_fp16"]["median_us"], 4)
     out["block_bf16_over_fp16"] = round(out["block_bf16"]["median_us"] / out["block_fp16"]["median_us"], 4)
     out["block_bf16_over_fp16_two_launch"] = round(out["block_bf16"]["median_us"] / out["block_fp16_two_launch"]["median_us"], 4)
+    out["block_bf16_joint_over_fp16"] = round(out["block_bf16_joint"]["median_us"] / out["block_fp16"]["median_us"], 4)
+    # what the joint launch saves per block call, each dtype against its own two-launch form of the same rounds
+    out["fp16_joint_saving_us"] = round(out["block_fp16_two_launch"]["median_us"] - out["block_fp16"]["median_us"], 3)
+    out["bf16_joint_saving_us"] = round(out["block_bf16"]["median_us"] - out["block_bf16_joint"]["median_us"], 3)
+    out["bf16_two_launch_spread_us"] = round(out["block_bf16"]["max_us"] - out["block_bf16"]["min_us"], 3)
     print(json.dumps(out))
 
 
@@ -161,7 +173,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--replays", type=int, default=31)
     ap.add_argument("--batch", type=int, default=bench.M)
-    ap.add_argument("--once", choices=["fp16", "bf16"], default=None)
+    ap.add_argument("--once", choices=["fp16", "bf16", "block_fp16", "block_fp16_two_launch", "block_bf16", "block_bf16_joint"], default=None)
     ap.add_argument("--block", action="store_true", help="time the fused norm + quantise pass and the norm -> MLP block, bf16 against fp16")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -169,6 +181,16 @@ def main():
     device = torch.device("cuda", 0)
     torch.cuda.set_device(device)
     side = torch.cuda.Stream()
+    if args.once and args.once.startswith("block_"):
+        dt = torch.float16 if "fp16" in args.once else torch.bfloat16
+        f = build_block(dt, device, args.batch, args.bit, args.steps, side, args.once in ("block_fp16", "block_bf16_joint"))
+        with torch.cuda.stream(side):
+            for _ in range(50):
+                f[1]()
+                f[0].replay()
+        torch.cuda.synchronize()
+        print(f"{args.once}: 50 replays of {args.steps} block calls, joint gate / up launch: {f[3]}")
+        return
     if args.block:
         return block_mode(args, device, side)
     dtypes = {"fp16": torch.float16, "bf16": torch.bfloat16}

@@ -14,6 +14,9 @@ TARGETS = [
     # gemm_wreg.hip compiled a second time, the bf16 forms: the container is the EIGHTH template argument (`bool BF`, Lb1E in the mangled
     # name).  Their lines carry a leading "bf16 " tag, the fields and the checks are the same
     ("gemm_wreg_bf16.hip", "gemm_wreg_kernel", WREG_ARGS, "MB={0} WNB={1} NSTAGE={2} D={3} Q={4} L={5} ABL={6}", 6, "gemm_wreg.hip"),
+    # ... and a third time, the bf16 forms of the joint gate / up launch (ABL=90 AND Lb1E): selected ONLY by its own file name - the
+    # gemm_wreg.hip invocation keeps listing exactly what it listed.  Here ABL=90 is the product form, not an ablation: a hit fails the check
+    ("gemm_wreg_bf16_pair.hip", "gemm_wreg_kernel", WREG_ARGS, "MB={0} WNB={1} NSTAGE={2} D={3} Q={4} L={5} ABL={6}", 6, "gemm_wreg_bf16_pair.hip", ("90",)),
     ("gemm_w8a16.hip", "gemm_w8a16_kernel", r"ILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)", "w8a16 MB={0} WNB={1} NSTAGE={2} D={3} L={4} ABL={5}", 5, "gemm_w8a16.hip"),
 ]
 
@@ -33,14 +36,14 @@ def regs(tok):
 def main():
     bad = 0
     only = set(sys.argv[1:])                                  # optional: source file names to restrict the check to
-    for fname, kname, tag_re, tag_fmt, abl_idx, under in TARGETS:
-        if only and under not in only:
+    for fname, kname, tag_re, tag_fmt, abl_idx, under, *forms in TARGETS:
+        if (only and under not in only) or (not only and forms):          # (a unit with product forms under ABL != 0: by its own name only)
             continue
-        bad += check(fname, kname, tag_re, tag_fmt, abl_idx)
+        bad += check(fname, kname, tag_re, tag_fmt, abl_idx, forms[0] if forms else ())
     return 1 if bad else 0
 
 
-def check(fname, kname, tag_re, tag_fmt, abl_idx):
+def check(fname, kname, tag_re, tag_fmt, abl_idx, forms=()):
     src = os.path.join(ROOT, "mixq_amd", "csrc", fname)
     with tempfile.TemporaryDirectory() as td:
         subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", src, "-save-temps", "-o", "x.o"], cwd=td,
@@ -128,7 +131,7 @@ def check(fname, kname, tag_re, tag_fmt, abl_idx):
                 if t.startswith("scratch_"): notes.append((i, t))
         sc = re.search(r"; ScratchSize: (\d+)", body)
         tag = re.search(tag_re, name).groups()
-        abl = tag[abl_idx] != "0"
+        abl = tag[abl_idx] != "0" and tag[abl_idx] not in forms          # (forms: ABL values that are product kernels of this unit)
         bf16 = len(tag) > abl_idx + 1 and tag[abl_idx + 1] == "1"
         print(f"{'bf16 ' if bf16 else ''}{tag_fmt.format(*tag)}: ring registers {len(loaded)}, in-flight LDS copies {len(lds_hits)}, "
               f"suspicious {len(hits)}" + ("  (ablation build: ignored)" if abl and hits else "") +
