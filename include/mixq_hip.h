@@ -144,8 +144,8 @@ int mixq_device_info(char* buf_host, int cap);
  * mixq_quant_known_amax_bf16.  Pad columns of x_out / w_out (>= n_out) may hold anything, NaN patterns included: they are masked.
  * Served layouts: MIXQ_X_PACKED | MIXQ_W_F16X64 (int8) and MIXQ_XW_F6X128 (4-bit), at every batch size, by the weights-in-registers
  * kernels; plain / P16X64 layouts, nibble-packed int4 and MIXQ_ACT_SILU_PAIR answer MIXQ_ESHAPE.  A configuration forced with
- * mixq_gemm_set_config that has no bf16 form answers MIXQ_EINVAL before any launch.  Not (yet) in bf16: mixq_gemm_w8a16,
- * mixq_gemm_i8 / mixq_dequant.  MIXQ_ACT_SILU_PAIR stays refused by THESE entry points (pinned behaviour); the joint gate / up launch in
+ * mixq_gemm_set_config that has no bf16 form answers MIXQ_EINVAL before any launch.  Not (yet) in bf16: mixq_gemm_i8 / mixq_dequant
+ * (the weight-only GEMM has bf16 entry points of its own since ABI 1.6: "bf16 weight-only layers" below).  MIXQ_ACT_SILU_PAIR stays refused by THESE entry points (pinned behaviour); the joint gate / up launch in
  * bf16 has entry points of its own (ABI 1.5 below).
  *
  * ---- bf16 RMSNorm (ABI 1.4): mixq_rmsnorm_bf16, mixq_rmsnorm_quant_fused_bf16, mixq_rmsnorm_quant_fused_masked_bf16 ----
@@ -473,9 +473,33 @@ int mixq_gemm_w8a16(const uint16_t* x, int ldx, const uint8_t* w_packed, const u
                     uint16_t* y, int ldy, int M, int N, int K, mixq_stream_t stream);
 int mixq_gemm_w8a16_addend(const uint16_t* x, int ldx, const uint8_t* w_packed, const uint16_t* scale_col, const uint16_t* addend, int lda,
                            const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int K, mixq_stream_t stream);
-int mixq_gemm_w8a16_set_config(int cfg);             /* tuning: force a tile config, -1 = automatic */
+int mixq_gemm_w8a16_set_config(int cfg);             /* tuning: force a tile config, -1 = automatic; serves the fp16 and the bf16 forms */
 int mixq_gemm_w8a16_num_configs(void);
 int mixq_gemm_w8a16_config_name(int cfg, char* buf, int cap);
+
+/* ---- bf16 weight-only layers (ABI 1.6): mixq_pack_w8a16_bf16, mixq_gemm_w8a16_bf16, mixq_gemm_w8a16_addend_bf16 ----
+ * The argument lists, the shape and alignment refusals and their order are exactly those of the fp16 twins above (K % 64, N % 4, ldx / ldy /
+ * lda, x 16-byte, y and addend 8-byte aligned).  mixq_version() does not tell: callers probe for the symbols.  The contract is fixed by
+ * decision (the reference has no bf16 path, and EETQ parity is unpinned anyway):
+ *   bfloat16: x, addend, y            fp16 as ever: scale_col, bias            q_weight int8 [K,N] and checkpoints: unchanged
+ *   weights   every int8 weight enters v_mfma_f32_16x16x32_bf16 as bf16(q), EXACTLY (all integers of [-128, 127] are bf16 values); no
+ *             rank-one "(q + 128), minus 128 * sum(x)" correction - it cancels in fp32 and would not be the contraction named here
+ *   acc       fp32 MFMA accumulation of x * q; the order is free, as for fp16
+ *   epilogue  the fp16 one with the container swapped: fp32 throughout, the addend first, then the bias, ONE rounding (v_cvt_pk_bf16_f32, RNE)
+ *               y[m,n] = RNE_bf16( acc[m,n] * float(scale_col[n]) (+ float(addend[m,n])) (+ float(bias[n])) )
+ *             nothing saturates: past the largest finite bf16 the result is inf.
+ * The weight image of mixq_pack_w8a16_bf16 has the MIXQ_FMT_F16X64 tile order of mixq_pack_w8a16 (16 channels x 64 k per KiB block, byte
+ * c * 256 + r * 16 + b), round16(N) * K bytes, but holds TWO'S-COMPLEMENT bytes (q itself; padding rows 0): the fp16 image is offset-binary
+ * because that is what ITS conversion wants.  The two images are not interchangeable and nothing in the bytes tells them apart: an image goes
+ * to the GEMM of the container it was packed for (a layer has one dtype, hence still one resident image).
+ * All nine product tilings have a bf16 form, with and without the addend.  The in-workgroup K-split kernel (configuration
+ * "w8a16_decode32", explicit-only) has none: with it forced the bf16 GEMM entry points answer MIXQ_EINVAL before anything is launched and
+ * ahead of the M == 0 early-out, like a forced tiling without a bf16 form in mixq_gemm_i8_fused_bf16. */
+int mixq_pack_w8a16_bf16(const int8_t* q_weight_kn, uint8_t* packed, int K, int N, mixq_stream_t stream);
+int mixq_gemm_w8a16_bf16(const uint16_t* x, int ldx, const uint8_t* w_packed, const uint16_t* scale_col, const uint16_t* bias,
+                         uint16_t* y, int ldy, int M, int N, int K, mixq_stream_t stream);
+int mixq_gemm_w8a16_addend_bf16(const uint16_t* x, int ldx, const uint8_t* w_packed, const uint16_t* scale_col, const uint16_t* addend, int lda,
+                                const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int K, mixq_stream_t stream);
 
 /* ---- stream-K workspace ---------------------------------------------------------------------------------
  * The stream-K form of the GEMM (opt-in through mixq_gemm_set_config) hands

@@ -112,6 +112,9 @@ SIGNATURES.update({
     "mixq_gemm_i4_pair_bf16": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "mixq_gemm_pair_supported_bf16": [_I, _I, _I, _I, _I],
 })
+# ABI 1.6: the weight-only W8A16 layers in bfloat16 (x, addend, y bfloat16; the fp16 twins' argument lists)
+W8A16_BF16 = ("mixq_pack_w8a16_bf16", "mixq_gemm_w8a16_bf16", "mixq_gemm_w8a16_addend_bf16")
+SIGNATURES.update({name + "_bf16": SIGNATURES[name] for name in ("mixq_pack_w8a16", "mixq_gemm_w8a16", "mixq_gemm_w8a16_addend")})
 RESTYPES = {"mixq_gemm_workspace_bytes": C.c_longlong}
 
 
@@ -165,7 +168,7 @@ def load():
         except AttributeError as e:
             if name in TUNING_ONLY:
                 continue                                   # the product library: no trace stamps, no tile-order knob
-            if name in PAIR_BF16:
+            if name in PAIR_BF16 or name in W8A16_BF16:
                 continue                                   # a library of an earlier ABI minor (mixq_version() does not tell): callers probe, mixlib.FusedLinear says so
             raise MixqBuildError(f"{LIB_PATH} does not export {name}; rebuild it") from e
         fn.argtypes = argtypes

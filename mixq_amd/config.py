@@ -44,7 +44,7 @@ class MixqConfig:
     # reference's, or torch.bfloat16: DESIGN.md section 2).  x_scale, scale_col, bias, sigma and the weight_cache buffer are float16 in
     # either case; y, x_out / activation_outliers and an addend / multiplier follow this switch.  Served in bfloat16: MixLinear_GEMM
     # (W8A8 and W4A4) and, behind `fused_bf16` below, FasterTransformerRMSNorm and MixLlamaMLP (its joint gate / up launch behind
-    # `joint_gate_up_bf16` on top of that); not (yet): weight_only layers.
+    # `joint_gate_up_bf16` on top of that) and, behind `w8a16_bf16`, weight_only (W8A16) layers.
     act_dtype: torch.dtype = torch.float16
     # Opt-in to the bfloat16 forms of the fused modules (fused.py): with act_dtype=torch.bfloat16 and fused_bf16=True,
     # FasterTransformerRMSNorm runs the bf16 norm + extract + quantise pass (mixq_rmsnorm*_bf16) and MixLlamaMLP the two-launch route with the
@@ -58,6 +58,11 @@ class MixqConfig:
     # under the default flags); nothing else speaks against it.  Not part of key(): the joint image's identity already carries act_dtype,
     # and the switch selects a route, not an image.
     joint_gate_up_bf16: bool = False
+    # Opt-in to bfloat16 weight-only (W8A16) layers (mixq_gemm_w8a16_bf16, ABI 1.6): with act_dtype=torch.bfloat16 and w8a16_bf16=True a
+    # MixLinear_GEMM(weight_only=True) is built and runs on bf16 x - GPT-J's fc_out, MixGPTJMLP, `extra_weight_only=` layers.  The default is
+    # off ONLY because the ValueError for such a layer under a bfloat16 config is pinned behaviour; nothing else speaks against it.  Without
+    # act_dtype=torch.bfloat16 the switch does nothing.  Not part of key(): it selects no GEMM plan and no joint image.
+    w8a16_bf16: bool = False
 
     def __post_init__(self):
         if self.act_dtype not in (torch.float16, torch.bfloat16):

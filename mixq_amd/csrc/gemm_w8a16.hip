@@ -23,6 +23,14 @@
 //    per k-step (in its middle: stage kt+1 is first needed by the second MFMA step), X fragments refilled in place behind
 //    their last MFMA, the conversion of the NEXT MFMA step's weight fragments issued behind the MFMAs of the current one
 //    (1 VALU per MFMA at MB = 8: what a wave co-issues for free, tools/ubench_mfma_valu.hip).
+//
+// The bfloat16 forms (x, addend, y in bfloat16; scale_col and bias fp16 as ever: include/mixq_hip.h, "bf16 weight-only layers") are THIS file
+// compiled a second time as gemm_w8a16_bf16.hip (MIXQ_WO_BF16_TU), the container a trailing template parameter there - a translation unit and
+// GPU code object of their own, as gemm_wreg_bf16.hip is for gemm_wreg.hip; in this file's own object BF is the constant `false` and the
+// kernels keep the names and the instructions they had.  What differs in the k loop is the conversion: the 0x6400 trick has no bfloat16
+// counterpart (a bf16 binade holds 128 integers, and gfx950 has no packed bf16 add), so the bf16 image holds q itself (two's complement),
+// and four weights become v_cvt_f32_i32 with a sign-extended byte select (SDWA) x 4 + v_cvt_pk_bf16_f32 x 2: bf16(q) exactly - every integer
+// of [-128, 127] is a bf16 value - in 6 VALU per four weights against 4, into v_mfma_f32_16x16x32_bf16, whose lane maps are the f16 ones.
 #include "common.h"
 #include <stdio.h>
 #include <type_traits>
@@ -47,6 +55,9 @@ __device__ __forceinline__ void wo_glds16(const uint8_t* gsrc, uint8_t* lds_wave
 __device__ __forceinline__ int wo_xpos(int t, int q) { return q ^ ((t >> 1) & 5); }
 
 typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+typedef __bf16 wo_bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 wo_bf16x2 __attribute__((ext_vector_type(2)));
+typedef float wo_f32x2 __attribute__((ext_vector_type(2)));
 
 template <int I, int N, class F> __device__ __forceinline__ void wo_static_for(F&& f) {
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); wo_static_for<I + 1, N>(f); }
@@ -61,15 +72,36 @@ __device__ __forceinline__ void cvt_u8x4(uint32_t d, uint32_t& o0, uint32_t& o1)
     o1 = __builtin_bit_cast(uint32_t, __builtin_bit_cast(h2_t, p1) - off);
 }
 
+// 4 two's-complement bytes -> 4 bfloat16 (two dwords), exactly: plain C, so that the compiler owns the SDWA hazards
+__device__ __forceinline__ uint32_t wo_cvt_pk_bf16(float lo, float hi) {        // round-to-nearest-even: v_cvt_pk_bf16_f32
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(wo_f32x2{lo, hi}, wo_bf16x2));
+}
+__device__ __forceinline__ void cvt_s8x4_bf16(uint32_t d, uint32_t& o0, uint32_t& o1) {
+    const float f0 = static_cast<float>(static_cast<int8_t>(d)), f1 = static_cast<float>(static_cast<int8_t>(d >> 8));
+    const float f2 = static_cast<float>(static_cast<int8_t>(d >> 16)), f3 = static_cast<float>(static_cast<int8_t>(d >> 24));
+    o0 = wo_cvt_pk_bf16(f0, f1);
+    o1 = wo_cvt_pk_bf16(f2, f3);
+}
+
 // MB: 16-row token blocks per tile (BM = 16 MB), WNB: 16-channel weight blocks per wave (BN = 64 WNB), NSTAGE: X ring depth,
 // D: weight register ring depth (k-steps), LOADERS: DMA waves.  ABL (tuning only): 0 normal, 1 no weight loads, 2 no X traffic,
 // 3 MFMA only, 4 MFMA + conversions (results of 1-4 are garbage), 5 no prologue ramp in the loader.
 // ADD: the form with an addend in the epilogue (mixq_gemm_w8a16_addend), an instantiation of its own: ADD = false is, instruction for
 // instruction, the kernel without the argument (the k loop sits at the edge of its register budget, and a run-time branch behind it moved
 // its register allocation and hazard padding).
-template <int MB, int WNB, int NSTAGE, int D, int LOADERS, int ABL = 0, bool ADD = false>
+// BF (the 16-bit container of x, addend and y; see the head of the file) exists as a template parameter only where this file is compiled as
+// gemm_w8a16_bf16.hip: here the kernels keep their seven-argument names, and the fp16 code object the instructions it had.
+#ifdef MIXQ_WO_BF16_TU
+#define MIXQ_WO_BF_TPARAM , bool BF
+#else
+#define MIXQ_WO_BF_TPARAM
+#endif
+template <int MB, int WNB, int NSTAGE, int D, int LOADERS, int ABL = 0, bool ADD = false MIXQ_WO_BF_TPARAM>
 __global__ __launch_bounds__((WO_CW + LOADERS) * 64) void gemm_w8a16_kernel(const WoArgs a)
 {
+#ifndef MIXQ_WO_BF16_TU
+    constexpr bool BF = false;
+#endif
     constexpr int CW = WO_CW, NT = (CW + LOADERS) * 64;
     constexpr int BM = MB * 16, WN = WNB * 16, BN = CW * WN;
     constexpr int STAGE_BYTES = MB * 2048;               // 16 MB rows x 128 bytes
@@ -260,7 +292,8 @@ __global__ __launch_bounds__((WO_CW + LOADERS) * 64) void gemm_w8a16_kernel(cons
             if constexpr (ABL != 3) {
                 const int i = u >> 1, d = u & 1;
                 uint32_t o0, o1;
-                cvt_u8x4(static_cast<uint32_t>(wq[C][i][2 * S + d]), o0, o1);
+                if constexpr (BF) cvt_s8x4_bf16(static_cast<uint32_t>(wq[C][i][2 * S + d]), o0, o1);
+                else cvt_u8x4(static_cast<uint32_t>(wq[C][i][2 * S + d]), o0, o1);
                 wc[S][i][2 * d] = o0; wc[S][i][2 * d + 1] = o1;
             }
         };
@@ -276,9 +309,14 @@ __global__ __launch_bounds__((WO_CW + LOADERS) * 64) void gemm_w8a16_kernel(cons
 #pragma unroll
             for (int j = 0; j < MB; ++j) {
 #pragma unroll
-                for (int i = 0; i < WNB; ++i)
-                    acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wc[S][i]), __builtin_bit_cast(f16x8, xf[j]),
-                                                                       acc[j][i], 0, 0, 0);
+                for (int i = 0; i < WNB; ++i) {
+                    if constexpr (BF)
+                        acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(wo_bf16x8, wc[S][i]), __builtin_bit_cast(wo_bf16x8, xf[j]),
+                                                                            acc[j][i], 0, 0, 0);
+                    else
+                        acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wc[S][i]), __builtin_bit_cast(f16x8, xf[j]),
+                                                                           acc[j][i], 0, 0, 0);
+                }
                 __builtin_amdgcn_sched_barrier(0);
                 xread(rslot, j, xo);
 #pragma unroll
@@ -392,6 +430,10 @@ __global__ __launch_bounds__((WO_CW + LOADERS) * 64) void gemm_w8a16_kernel(cons
             o[0] = h2f(static_cast<uint16_t>(v.x & 0xffffu)); o[1] = h2f(static_cast<uint16_t>(v.x >> 16));
             o[2] = h2f(static_cast<uint16_t>(v.y & 0xffffu)); o[3] = h2f(static_cast<uint16_t>(v.y >> 16));
         };
+        auto unpack4_act = [](u32x2 v, float* o) {                               // the addend: the activations' container (scale_col and bias are fp16 in either form)
+            o[0] = a2f<BF>(static_cast<uint16_t>(v.x & 0xffffu)); o[1] = a2f<BF>(static_cast<uint16_t>(v.x >> 16));
+            o[2] = a2f<BF>(static_cast<uint16_t>(v.y & 0xffffu)); o[3] = a2f<BF>(static_cast<uint16_t>(v.y >> 16));
+        };
 #pragma unroll
         for (int i = 0; i < WNB; ++i) {
             const int nloc = wave * WN + i * 16 + lq * 4, n = n0 + nloc;
@@ -402,7 +444,9 @@ __global__ __launch_bounds__((WO_CW + LOADERS) * 64) void gemm_w8a16_kernel(cons
 #pragma unroll
             for (int j = 0; j < MB; ++j) {
                 float v[4], ad[4];
-                if constexpr (ADD) unpack4(av[j][i], ad);
+                if constexpr (ADD) {
+                    if constexpr (BF) unpack4_act(av[j][i], ad); else unpack4(av[j][i], ad);
+                }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     v[e] = acc[j][i][e] * swv[e];
@@ -410,8 +454,13 @@ __global__ __launch_bounds__((WO_CW + LOADERS) * 64) void gemm_w8a16_kernel(cons
                     if (has_bias) v[e] += bv[e];
                 }
                 u32x2 o;
-                o.x = static_cast<uint32_t>(f2h(v[0])) | (static_cast<uint32_t>(f2h(v[1])) << 16);
-                o.y = static_cast<uint32_t>(f2h(v[2])) | (static_cast<uint32_t>(f2h(v[3])) << 16);
+                if constexpr (BF) {                                          // ONE rounding, to nearest even: v_cvt_pk_bf16_f32
+                    o.x = wo_cvt_pk_bf16(v[0], v[1]);
+                    o.y = wo_cvt_pk_bf16(v[2], v[3]);
+                } else {
+                    o.x = static_cast<uint32_t>(f2h(v[0])) | (static_cast<uint32_t>(f2h(v[1])) << 16);
+                    o.y = static_cast<uint32_t>(f2h(v[2])) | (static_cast<uint32_t>(f2h(v[3])) << 16);
+                }
                 *reinterpret_cast<u32x2*>(lds + (j * 16 + lm) * OPITCH + nloc * 2) = o;
             }
         }
@@ -451,6 +500,7 @@ __global__ __launch_bounds__((WO_CW + LOADERS) * 64) void gemm_w8a16_kernel(cons
     }
 }
 
+#ifndef MIXQ_WO_BF16_TU                                  // (no bf16 form: explicit-only and slower than the 32 x 64 tiling; the bf16 entry points refuse it)
 // ---- small-batch (decode) form: M <= 32 ----------------------------------------------------------------------------
 // A weight stream, like gemm_skinny.hip: one workgroup per 32 output channels, its 8 waves split K, fragments go
 // global -> VGPR -> MFMA (weights: the packed offset-binary image; activations: the caller's fp16 rows, L2-resident), no LDS
@@ -574,8 +624,17 @@ __global__ __launch_bounds__(WSK * 64, 2) void gemm_w8a16_skinny_kernel(const Wo
     }
 }
 
+#endif  // !MIXQ_WO_BF16_TU
+
 // One-time re-tiling of the checkpoint's [K,N] int8 matrix into offset-binary MIXQ_FMT_F16X64 (rows = output channels): thread t
 // writes the t-th 16-byte piece of the image, piece (kb, rb, c, r) = channel 16 rb + r, k = 64 kb + 16 c .. + 16.
+// Compiled as gemm_w8a16_bf16.hip: the same tile order holding q itself (two's complement, what the bf16 conversion wants), padding rows 0.
+#ifdef MIXQ_WO_BF16_TU
+constexpr int WO_PACK_OFF = 0;
+#define pack_w8a16_kernel pack_w8a16_s8_kernel
+#else
+constexpr int WO_PACK_OFF = 128;
+#endif
 __global__ __launch_bounds__(256) void pack_w8a16_kernel(const int8_t* __restrict__ qkn, uint8_t* __restrict__ dst, int K, int N, int rows16)
 {
     const long long t = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
@@ -586,7 +645,8 @@ __global__ __launch_bounds__(256) void pack_w8a16_kernel(const int8_t* __restric
     const int rb = rem >> 6, c = (rem >> 4) & 3, r = rem & 15;
     const int n = rb * 16 + r;
     const int k0 = kb * 64 + c * 16;
-    uint32_t w[4] = {0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};      // q = 0 for padding rows
+    constexpr uint32_t ZERO4 = static_cast<uint32_t>(WO_PACK_OFF) * 0x01010101u;
+    uint32_t w[4] = {ZERO4, ZERO4, ZERO4, ZERO4};                               // q = 0 for padding rows
     if (n < N) {
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
@@ -594,13 +654,47 @@ __global__ __launch_bounds__(256) void pack_w8a16_kernel(const int8_t* __restric
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int q = qkn[static_cast<size_t>(k0 + 4 * d + e) * N + n];
-                v |= static_cast<uint32_t>((q + 128) & 0xff) << (8 * e);
+                v |= static_cast<uint32_t>((q + WO_PACK_OFF) & 0xff) << (8 * e);
             }
             w[d] = v;
         }
     }
     reinterpret_cast<uint4*>(dst)[t] = make_uint4(w[0], w[1], w[2], w[3]);
 }
+
+#ifdef MIXQ_WO_BF16_TU
+// ---- the bf16 forms (this file compiled as gemm_w8a16_bf16.hip) -----------------------------------------------------------------
+// BF = true: the nine product tilings with the template arguments of the same rows of g_wo (whose geometry the launch reads), each
+// without and with the addend.  No ablation forms, no in-workgroup K-split kernel.
+struct WoBf16 { void (*k)(const WoArgs); void (*ka)(const WoArgs); };
+#define MIXQ_WOB(MBv, WNBv, NS, Dv, LD) { gemm_w8a16_kernel<MBv, WNBv, NS, Dv, LD, 0, false, true>, gemm_w8a16_kernel<MBv, WNBv, NS, Dv, LD, 0, true, true> }
+const WoBf16 g_wo_bf16[] = {
+    MIXQ_WOB(8, 3, 8, 3, 2), MIXQ_WOB(8, 2, 8, 4, 2), MIXQ_WOB(4, 2, 12, 4, 2), MIXQ_WOB(4, 4, 12, 3, 2), MIXQ_WOB(4, 3, 12, 4, 2),
+    MIXQ_WOB(4, 1, 8, 4, 1), MIXQ_WOB(8, 3, 8, 4, 2), MIXQ_WOB(8, 3, 6, 3, 1), MIXQ_WOB(2, 1, 8, 5, 1),
+};
+constexpr int NUM_WO_BF16 = sizeof(g_wo_bf16) / sizeof(g_wo_bf16[0]);
+}  // namespace
+
+// the kernel (launch handle) of product tiling c in its bf16 form, or nullptr.  WoArgs is this file's struct in either translation unit, so
+// gemm_w8a16.hip fills the argument block and launches the handle.
+const void* mixq_wo_bf16_kernel(int c, bool with_addend)
+{
+    if (c < 0 || c >= NUM_WO_BF16) return nullptr;
+    return reinterpret_cast<const void*>(with_addend ? g_wo_bf16[c].ka : g_wo_bf16[c].k);
+}
+// the two's-complement image of mixq_pack_w8a16_bf16 (arguments already checked)
+int mixq_wo_pack_s8(const int8_t* q_weight_kn, uint8_t* packed, int K, int N, hipStream_t st)
+{
+    const int rows16 = (N + 15) & ~15;
+    const long long total = static_cast<long long>(rows16) * (K >> 4);
+    hipLaunchKernelGGL(pack_w8a16_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, st, q_weight_kn, packed, K, N, rows16);
+    return mixq_launch_status();
+}
+#else
+}  // namespace
+const void* mixq_wo_bf16_kernel(int c, bool with_addend);   // gemm_w8a16_bf16.hip
+int mixq_wo_pack_s8(const int8_t* q_weight_kn, uint8_t* packed, int K, int N, hipStream_t st);
+namespace {
 
 struct WoConfig {
     const char* name; int mb, wnb, nstage, loaders;
@@ -669,14 +763,19 @@ extern "C" int mixq_pack_w8a16(const int8_t* q_weight_kn, uint8_t* packed, int K
     return mixq_launch_status();
 }
 
-extern "C" int mixq_gemm_w8a16_addend(const uint16_t* x, int ldx, const uint8_t* w_packed, const uint16_t* scale_col, const uint16_t* addend,
-                                      int lda, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int K, mixq_stream_t stream)
+// every W8A16 GEMM entry point: bf16 = the `_bf16` ones (x, addend, y bfloat16; the kernels of gemm_w8a16_bf16.hip, w_packed from
+// mixq_pack_w8a16_bf16)
+static int wo_gemm(bool bf16, const uint16_t* x, int ldx, const uint8_t* w_packed, const uint16_t* scale_col, const uint16_t* addend,
+                   int lda, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int K, mixq_stream_t stream)
 {
     if (M < 0 || N < 0 || K <= 0 || (M > 0 && N > 0 && (!x || !w_packed || !scale_col || !y))) return MIXQ_EINVAL;
     if ((K % 64) || (N & 3) || (ldy & 3) || ldy < N || ldx < K || (ldx & 7) || (addend && (lda < N || (lda & 3)))) return MIXQ_ESHAPE;
     if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(y) & 7) || (reinterpret_cast<uintptr_t>(addend) & 7)) return MIXQ_EINVAL;
-    if (M == 0 || N == 0) return MIXQ_OK;
     const int g_wo_forced = g_wo_forced_dev.get();
+    // a forced configuration without a bf16 form (the in-workgroup K-split kernel, a tuning build's ablation forms): said before anything is
+    // launched and ahead of the empty-problem return, like a forced tiling without one in mixq_gemm_i8_fused_bf16
+    if (bf16 && g_wo_forced >= 0 && !mixq_wo_bf16_kernel(g_wo_forced, addend != nullptr)) return MIXQ_EINVAL;
+    if (M == 0 || N == 0) return MIXQ_OK;
     WoArgs a;
     a.x = x; a.w = w_packed; a.sw = scale_col; a.bias = bias; a.y = y;
     a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldy = ldy; a.tiles_m = a.tiles_n = 0; a.wblocks = (N + 15) >> 4;
@@ -692,17 +791,44 @@ extern "C" int mixq_gemm_w8a16_addend(const uint16_t* x, int ldx, const uint8_t*
     a.tiles_m = wo_cdiv(M, bm); a.tiles_n = wo_cdiv(N, bn);
     const size_t ring = static_cast<size_t>(g.nstage) * g.mb * 2048, stg = static_cast<size_t>(bm) * (bn * 2 + 16);
     const size_t shm = ring > stg ? ring : stg;
-    void (*const kern)(const WoArgs) = addend ? g.ka : g.k;
+    void (*const kern)(const WoArgs) = bf16 ? reinterpret_cast<void (*)(const WoArgs)>(const_cast<void*>(mixq_wo_bf16_kernel(c, addend != nullptr)))
+                                            : (addend ? g.ka : g.k);
     if (!kern) return MIXQ_EINVAL;
     if (int rc = mixq_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), shm)) return rc;
     hipLaunchKernelGGL(kern, dim3(a.tiles_m * a.tiles_n), dim3((WO_CW + g.loaders) * 64), shm, mixq_stream(stream), a);
     return mixq_launch_status();
 }
 
+extern "C" int mixq_gemm_w8a16_addend(const uint16_t* x, int ldx, const uint8_t* w_packed, const uint16_t* scale_col, const uint16_t* addend,
+                                      int lda, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int K, mixq_stream_t stream)
+{
+    return wo_gemm(false, x, ldx, w_packed, scale_col, addend, lda, bias, y, ldy, M, N, K, stream);
+}
+
 extern "C" int mixq_gemm_w8a16(const uint16_t* x, int ldx, const uint8_t* w_packed, const uint16_t* scale_col, const uint16_t* bias,
                                uint16_t* y, int ldy, int M, int N, int K, mixq_stream_t stream)
 {
     return mixq_gemm_w8a16_addend(x, ldx, w_packed, scale_col, nullptr, 0, bias, y, ldy, M, N, K, stream);
+}
+
+// ---- the bf16 twins (ABI 1.6): the argument lists and refusals of the three above; x, addend and y hold bfloat16 ----------------
+extern "C" int mixq_pack_w8a16_bf16(const int8_t* q_weight_kn, uint8_t* packed, int K, int N, mixq_stream_t stream)
+{
+    if (K <= 0 || N <= 0 || !q_weight_kn || !packed) return MIXQ_EINVAL;
+    if (K % 64) return MIXQ_ESHAPE;
+    return mixq_wo_pack_s8(q_weight_kn, packed, K, N, mixq_stream(stream));
+}
+
+extern "C" int mixq_gemm_w8a16_addend_bf16(const uint16_t* x, int ldx, const uint8_t* w_packed, const uint16_t* scale_col, const uint16_t* addend,
+                                           int lda, const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int K, mixq_stream_t stream)
+{
+    return wo_gemm(true, x, ldx, w_packed, scale_col, addend, lda, bias, y, ldy, M, N, K, stream);
+}
+
+extern "C" int mixq_gemm_w8a16_bf16(const uint16_t* x, int ldx, const uint8_t* w_packed, const uint16_t* scale_col, const uint16_t* bias,
+                                    uint16_t* y, int ldy, int M, int N, int K, mixq_stream_t stream)
+{
+    return wo_gemm(true, x, ldx, w_packed, scale_col, nullptr, 0, bias, y, ldy, M, N, K, stream);
 }
 
 extern "C" int mixq_gemm_w8a16_set_config(int cfg) {
@@ -716,3 +842,4 @@ extern "C" int mixq_gemm_w8a16_config_name(int cfg, char* buf, int cap) {
     snprintf(buf, cap, "%s", cfg == NUM_WO ? "w8a16_decode32" : g_wo[cfg].name);
     return MIXQ_OK;
 }
+#endif  // MIXQ_WO_BF16_TU

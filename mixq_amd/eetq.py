@@ -18,7 +18,7 @@ import torch
 from . import mixlib as _mixlib
 
 _backend = _mixlib
-_packed = {}          # (data_ptr, version, shape) -> (q_weight, packed weights), for callers that only hold q_weight (w8_a16_gemm).
+_packed = {}          # (data_ptr, version, shape, container) -> (q_weight, packed weights), for callers that only hold q_weight (w8_a16_gemm).
                       # The entry keeps q_weight itself alive: a key made of an address must not outlive the allocation it names.
 
 
@@ -80,18 +80,21 @@ def unprocess_weights(processed):
     return q
 
 
-def packed_weight(q_weight):
-    key = (q_weight.data_ptr(), q_weight._version, tuple(q_weight.shape))
+def packed_weight(q_weight, dtype=torch.float16):
+    """The kernel's image of q_weight for activations of `dtype` (float16: offset-binary, bfloat16: two's complement), packed once."""
+    key = (q_weight.data_ptr(), q_weight._version, tuple(q_weight.shape), dtype)
     e = _packed.get(key)
     if e is None:
         if len(_packed) > 256:
             _packed.clear()
-        e = _packed[key] = (q_weight, _backend.PackW8A16(q_weight))
+        e = _packed[key] = (q_weight, _backend.PackW8A16(q_weight) if dtype == torch.float16 else _backend.PackW8A16(q_weight, dtype))
     return e[1]
 
 
 def w8_a16_gemm(x, q_weight, scale_col, bias=None):
-    """y[..., N] = x[..., K] @ (q_weight[K,N] * scale_col[N]) (+ bias): linear.py:180."""
+    """y[..., N] = x[..., K] @ (q_weight[K,N] * scale_col[N]) (+ bias): linear.py:180.  x float16, or bfloat16 (then y is bfloat16;
+    scale_col and bias float16 in either case)."""
     K, N = q_weight.shape
-    y = _backend.W8A16Linear(x.reshape(-1, K), packed_weight(q_weight), scale_col.reshape(-1), bias, N, K)
+    wp = packed_weight(q_weight, torch.bfloat16) if x.dtype == torch.bfloat16 else packed_weight(q_weight)
+    y = _backend.W8A16Linear(x.reshape(-1, K), wp, scale_col.reshape(-1), bias, N, K)
     return y.reshape(x.shape[:-1] + (N,))

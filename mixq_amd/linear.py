@@ -201,8 +201,9 @@ class MixLinear_GEMM(nn.Module):
         # the model's activation dtype (config.py: act_dtype) - what bfloat16 does not serve is said here too, not by the first forward
         act_dtype = getattr(getattr(cache, "config", None), "act_dtype", torch.float16)
         if act_dtype == torch.bfloat16:
-            if weight_only:
-                raise ValueError("MixLinear_GEMM: weight_only (W8A16) layers have no bfloat16 form; use act_dtype=torch.float16")
+            if weight_only and not getattr(cache.config, "w8a16_bf16", False):
+                raise ValueError("MixLinear_GEMM: weight_only (W8A16) layers run in bfloat16 only with MixqConfig(w8a16_bf16=True) (opt-in, "
+                                 "config.py); use it or act_dtype=torch.float16")
             if bit == 8 and in_features % 64:
                 raise ValueError(f"MixLinear_GEMM: a bfloat16 W8A8 layer needs in_features % 64 == 0 - there is no plain-operand bfloat16 GEMM "
                                  f"(got {in_features} -> {out_features})")
@@ -262,7 +263,13 @@ class MixLinear_GEMM(nn.Module):
         if weight_only is True:
             # linear.py:102-106: EETQ's per-column symmetric int8 of W^T [K,N] (restated in mixq_amd/eetq.py)
             from . import eetq
-            int8_weight, scales = eetq.quant_weights(torch.t(linear.weight.data).contiguous().cpu(), torch.int8, False)
+            Wt = torch.t(linear.weight.data).contiguous().cpu()
+            if Wt.dtype == torch.bfloat16 and q.config.act_dtype == torch.bfloat16:
+                # quant_weights returns the scales in the weight's dtype: for bf16 weights `.half()` below would round scale_col twice
+                # (fp32 -> bf16 -> fp16).  Quantised from the fp32 image instead: scale_col = fp16(colabsmax / 128) computed in fp32.  An
+                # fp16 Linear takes the path it always took.
+                Wt = Wt.float()
+            int8_weight, scales = eetq.quant_weights(Wt, torch.int8, False)
             q.q_weight.copy_(int8_weight)
             q.scale_col.copy_(scales.half())
             if linear.bias is not None:
@@ -668,7 +675,7 @@ class MixLinear_GEMM(nn.Module):
     @torch.no_grad()
     def forward(self, x, cache=None, unfused=False, residual=None):
         """`residual` (an extension: the reference adds it in torch, modules/fused/block.py:32-33): a tensor of shape
-        x.shape[:-1] + (out_features,), of the layer's act_dtype (float16 for a weight-only layer), on x's device, with a contiguous last
+        x.shape[:-1] + (out_features,), of the layer's act_dtype, on x's device, with a contiguous last
         dimension - anything else raises RuntimeError.  It is the addend of the GEMM's fp32 epilogue, y = round(linear(x) + residual) with
         ONE rounding and no pass of its own, on every route: search phase / two calls, the frozen one-call forward, weight-only.  The
         result is a new tensor; the residual is only read (it should not be x itself: new outlier columns of x are zeroed in place).
@@ -723,9 +730,14 @@ class MixLinear_GEMM(nn.Module):
                 return y1.reshape(cache.shape)
         if self.weight_only is True:
             # linear.py:178-184 (w8_a16_gemm, then `y += bias`): here the bias rides in the GEMM epilogue
-            key = (id(self.q_weight), self.q_weight.data_ptr(), self.q_weight._version)
+            bf = self.act_dtype != torch.float16
+            if not bf and inputs.dtype == torch.bfloat16:    # (W8A16Linear would take it for a call of the bf16 form)
+                raise RuntimeError("MixLinear_GEMM: x must be float16")
+            # one dtype per layer, hence one resident image; a bf16 layer's key and pack call carry the container, an fp16 layer's are what
+            # they were
+            key = (id(self.q_weight), self.q_weight.data_ptr(), self.q_weight._version) + ((self.act_dtype,) if bf else ())
             if self._wpk is None or self._wpk_key != key:
-                self._wpk, self._wpk_key = _backend.PackW8A16(self.q_weight), key
+                self._wpk, self._wpk_key = _backend.PackW8A16(self.q_weight, *((self.act_dtype,) if bf else ())), key
             y = _backend.W8A16Linear(inputs, self._wpk, self.scale_col, self.bias, self.out_features, self.in_features, **radd)
             return y.reshape(cache.shape)
         qmax = 2 ** (self.bit - 1) - 1

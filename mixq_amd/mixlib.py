@@ -1061,14 +1061,28 @@ def layernorm_forward_cuda_extract_outliers_int4(x, weight, out, eps, ind, x_sca
 # ------------------------------------------------------------------------------------------------------------
 # weight-only W8A16 (the reference reaches it through EETQ, linear.py:9,102-106,178-184)
 # ------------------------------------------------------------------------------------------------------------
-def PackW8A16(q_weight_kn):
-    """Re-tile the checkpoint's int8 [K,N] weight for mixq_gemm_w8a16 (once per layer) -> uint8 [round16(N) * K]."""
+def _w8a16_entry(name):
+    """The bf16 twin of a W8A16 entry point (ABI 1.6), or a RuntimeError that says what is missing: no fall-back, no fp16 detour."""
+    if not hasattr(_capi.load(), name):
+        raise RuntimeError(f"mixq_amd.mixlib: {_capi.LIB_PATH} does not export {name} (the bfloat16 weight-only GEMM, ABI 1.6); rebuild it")
+    return name
+
+
+def PackW8A16(q_weight_kn, dtype=torch.float16):
+    """Re-tile the checkpoint's int8 [K,N] weight for mixq_gemm_w8a16 (once per layer) -> uint8 [round16(N) * K].
+    dtype: the activation container of the GEMM that will read the image - torch.float16 (offset-binary bytes, mixq_pack_w8a16) or
+    torch.bfloat16 (two's-complement bytes, mixq_pack_w8a16_bf16).  The image is tagged with it: W8A16Linear refuses a bf16 x on an image
+    that was not packed for bfloat16 (the bytes themselves do not tell)."""
     _dev_check(q_weight_kn)
     if q_weight_kn.dtype != torch.int8 or q_weight_kn.dim() != 2 or not q_weight_kn.is_contiguous():
         raise RuntimeError("PackW8A16: expected a contiguous int8 [K,N] tensor")
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError(f"PackW8A16: dtype must be torch.float16 or torch.bfloat16, got {dtype}")
     K, N = q_weight_kn.shape
     out = torch.empty(((N + 15) // 16 * 16) * K, dtype=torch.uint8, device=q_weight_kn.device)
-    _capi.call("mixq_pack_w8a16", q_weight_kn.data_ptr(), out.data_ptr(), K, N, _stream())
+    name = "mixq_pack_w8a16" if dtype == torch.float16 else _w8a16_entry("mixq_pack_w8a16_bf16")
+    _capi.call(name, q_weight_kn.data_ptr(), out.data_ptr(), K, N, _stream())
+    out._mixq_w8a16_dtype = dtype
     return out
 
 
@@ -1083,26 +1097,41 @@ def _overlap(a, b):
 
 def W8A16Linear(x, w_packed, scale_col, bias, N, K, out=None, addend=None):
     """y = x @ (q * scale_col) (+ addend) + bias with the weights from PackW8A16.  x fp16 [M,K] (row stride % 8 == 0).
-    addend (fp16 [M,N] on x's device, contiguous last dimension, row stride >= N and a multiple of 4 elements; read only): added in
+    A bfloat16 x selects the bf16 entry points (mixq_gemm_w8a16_bf16 / _addend_bf16): scale_col and bias stay float16, addend and `out` are
+    bfloat16, and w_packed must come from PackW8A16(q, torch.bfloat16) - an untagged or fp16 image is refused, not read as wrong numbers.
+    addend (x's dtype, [M,N] on x's device, contiguous last dimension, row stride >= N and a multiple of 4 elements; read only): added in
     the GEMM's fp32 epilogue in front of the bias and the ONE rounding (mixq_gemm_w8a16_addend) - the residual stream behind a weight-only
     down_proj / fc_out.  It may not overlap `out`.  Without it the call is mixq_gemm_w8a16, as before."""
     _dev_check(x, w_packed, scale_col, bias, addend)
-    if x.dtype != torch.float16 or scale_col.dtype != torch.float16:
+    bf16 = x.dtype == torch.bfloat16
+    if not bf16 and (x.dtype != torch.float16 or scale_col.dtype != torch.float16):
         raise RuntimeError("W8A16Linear: x and scale_col must be float16")
+    dt, sfx = x.dtype, ""
+    if bf16:
+        if scale_col.dtype != torch.float16 or (bias is not None and bias.dtype != torch.float16):
+            raise RuntimeError("W8A16Linear: scale_col and bias stay float16 with a bfloat16 x (include/mixq_hip.h, bf16 weight-only layers)")
+        if getattr(w_packed, "_mixq_w8a16_dtype", None) != torch.bfloat16:
+            raise RuntimeError("W8A16Linear: a bfloat16 x needs the weight image of PackW8A16(q_weight, torch.bfloat16) (two's-complement bytes); "
+                               "this one is untagged or was packed for float16 (offset-binary)")
+        _w8a16_entry("mixq_gemm_w8a16_bf16")
+        sfx = "_bf16"
+    elif getattr(w_packed, "_mixq_w8a16_dtype", None) == torch.bfloat16:
+        raise RuntimeError("W8A16Linear: this weight image was packed for bfloat16 (PackW8A16(q_weight, torch.bfloat16)); a float16 x needs "
+                           "the float16 image")
     x2 = x.reshape(-1, x.shape[-1])
     if x2.shape[1] != K or scale_col.numel() != N:
         raise RuntimeError("W8A16Linear: shape mismatch")
     if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.data_ptr() % 16:
         x2 = x2.contiguous()
     M = x2.shape[0]
-    y = out if out is not None else torch.empty((M, N), dtype=torch.float16, device=x.device)
+    y = out if out is not None else torch.empty((M, N), dtype=dt, device=x.device)
     if out is not None:
-        if out.dtype != torch.float16:
-            raise RuntimeError(f"W8A16Linear: `out` must be torch.float16, got {out.dtype}")
+        if out.dtype != dt:
+            raise RuntimeError(f"W8A16Linear: `out` must be {dt}, got {out.dtype}")
         _check_out(out, M, N, x.device, "W8A16Linear")
     if addend is not None:
-        if addend.dtype != torch.float16 or addend.device != x.device:
-            raise RuntimeError(f"W8A16Linear: addend must be torch.float16 on x's device ({x.device}), got {addend.dtype} on {addend.device}")
+        if addend.dtype != dt or addend.device != x.device:
+            raise RuntimeError(f"W8A16Linear: addend must be {dt} on x's device ({x.device}), got {addend.dtype} on {addend.device}")
         if addend.dim() != 2 or tuple(addend.shape) != (M, N) or addend.stride(1) != 1 or (M > 1 and (addend.stride(0) % 4 or addend.stride(0) < N)):
             raise RuntimeError(f"W8A16Linear: addend must be [{M}, {N}] with a contiguous last dimension and a row stride that is a multiple of 4 elements "
                                f"and at least {N} (got {tuple(addend.shape)} strides {tuple(addend.stride())})")
@@ -1110,9 +1139,9 @@ def W8A16Linear(x, w_packed, scale_col, bias, N, K, out=None, addend=None):
             raise RuntimeError("W8A16Linear: addend may not alias `out` (include/mixq_hip.h: mixq_gemm_w8a16_addend)")
         addend = _aligned_addend(addend)
         lda = addend.stride(0) if M > 1 else N               # (one row: any stride describes it)
-        _capi.call("mixq_gemm_w8a16_addend", x2.data_ptr(), x2.stride(0) if M else K, w_packed.data_ptr(), scale_col.data_ptr(), addend.data_ptr(),
+        _capi.call("mixq_gemm_w8a16_addend" + sfx, x2.data_ptr(), x2.stride(0) if M else K, w_packed.data_ptr(), scale_col.data_ptr(), addend.data_ptr(),
                    lda, _ptr(bias), y.data_ptr(), y.stride(0) if M else N, M, N, K, _stream())
         return y
-    _capi.call("mixq_gemm_w8a16", x2.data_ptr(), x2.stride(0) if M else K, w_packed.data_ptr(), scale_col.data_ptr(), _ptr(bias),
+    _capi.call("mixq_gemm_w8a16" + sfx, x2.data_ptr(), x2.stride(0) if M else K, w_packed.data_ptr(), scale_col.data_ptr(), _ptr(bias),
                y.data_ptr(), y.stride(0) if M else N, M, N, K, _stream())
     return y

@@ -18,6 +18,10 @@ TARGETS = [
     # gemm_wreg.hip invocation keeps listing exactly what it listed.  Here ABL=90 is the product form, not an ablation: a hit fails the check
     ("gemm_wreg_bf16_pair.hip", "gemm_wreg_kernel", WREG_ARGS, "MB={0} WNB={1} NSTAGE={2} D={3} Q={4} L={5} ABL={6}", 6, "gemm_wreg_bf16_pair.hip", ("90",)),
     ("gemm_w8a16.hip", "gemm_w8a16_kernel", r"ILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)", "w8a16 MB={0} WNB={1} NSTAGE={2} D={3} L={4} ABL={5}", 5, "gemm_w8a16.hip"),
+    # gemm_w8a16.hip compiled a second time, the bf16 weight-only forms: `bool ADD` is the seventh template argument (both forms of a tiling
+    # are checked and print the same fields, ADD appended), the container the EIGHTH (Lb1E) - the leading "bf16 " tag.  Under its own file name.
+    ("gemm_w8a16_bf16.hip", "gemm_w8a16_kernel", r"ILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E(?=Lb[01]ELb([01])E)Lb([01])E",
+     "w8a16 MB={0} WNB={1} NSTAGE={2} D={3} L={4} ABL={5} ADD={7}", 5, "gemm_w8a16_bf16.hip"),
 ]
 
 
