@@ -39,6 +39,16 @@ def _fmt_of(t):
     return getattr(t, "_mixq_fmt", FMT_PLAIN)
 
 
+def _served(t):
+    """Does `t` live on a device the kernel backend serves?  The backend's own answer (dev_check: a GPU tensor for the HIP module), as
+    forward() asks it for x - not `t.is_cuda` restated here."""
+    try:
+        _backend.dev_check(t)
+    except RuntimeError:
+        return False
+    return True
+
+
 def two_compl(x: Tensor, bits: int) -> Tensor:
     """Signed -> unsigned two's-complement field of `bits` bits (linear.py:12-13)."""
     return torch.where(x < 0, x + (1 << bits), x)
@@ -661,7 +671,7 @@ class MixLinear_GEMM(nn.Module):
             raise RuntimeError(f"MixLinear_GEMM: residual must be {dt} like the layer's activations (MixqConfig.act_dtype), got {residual.dtype}")
         if tuple(residual.shape) != want:
             raise RuntimeError(f"MixLinear_GEMM: residual must have shape {want} (x.shape[:-1] + (out_features,)), got {tuple(residual.shape)}")
-        if not residual.is_cuda or residual.device != x.device:
+        if not _served(residual) or residual.device != x.device:
             raise RuntimeError(f"MixLinear_GEMM: residual must be a GPU (HIP) tensor on x's device ({x.device}), got {residual.device}")
         if residual.stride(-1) != 1:
             raise RuntimeError(f"MixLinear_GEMM: residual must have a contiguous last dimension, got strides {tuple(residual.stride())}")
