@@ -190,7 +190,52 @@ int mixq_device_info(char* buf_host, int cap);
  *                  64x256 and 32x64 in both widths, 128x256 in int8) - ahead of
  *   8 MIXQ_OK      M == 0 or N == 0: nothing is launched.
  * mixq_gemm_pair_supported_bf16(M, N, K, bit, layout): 1 when the entry point of that width (bit 8 or 4) serves the problem with the
- * automatic choice, else 0.  mixq_version() still answers 1003; probe for the symbols. */
+ * automatic choice, else 0.  mixq_version() still answers 1003; probe for the symbols.
+ *
+ * ---- bf16 small-batch form (ABI 1.7): mixq_gemm_i8_decode_bf16, mixq_gemm_i4_decode_bf16, mixq_gemm_decode_pick_bf16,
+ *      mixq_linear_forward_decode_bf16 ----
+ * The small-batch ("decode") kernel of the fp16 entry points - M <= 32 token rows, one workgroup per 32 output channels, its 8 waves
+ * splitting K, no LDS staging - with the bfloat16 container: where the `_bf16` entry points above run the 32 x 64 weights-in-registers
+ * tiling (N / 64 workgroups), these run N / 32 workgroups x 8 waves.  Entry points of their own: what the `_bf16` ones accept, choose and
+ * write is pinned.  The argument lists are mixq_gemm_i8_fused_bf16's / mixq_gemm_i4_fused_bf16's; the contract is "bf16 layers" above, word
+ * for word - x_out, w_out, addend (the multiplier of MIXQ_ACT_SILU_MUL included) and y bfloat16; x_scale, scale_col and bias fp16; fp32
+ * throughout and ONE rounding (v_cvt_pk_bf16_f32, RNE):
+ *   z = acc * float(sx[m]) * float(sw[n]) + sum_j float(xo[m,j]) * float(wo[n,j]) + float(addend[m,n])
+ *   y = bf16( act(z) + float(bias[n]) );   MIXQ_ACT_SILU_MUL: y = bf16( (silu(z') + bias) * float(addend) ), z' without the addend
+ * acc is the exact int32 sum (the 8 waves' partial sums are added as integers).  The outlier tail runs on v_mfma_f32_32x32x16_bf16, 16
+ * columns per step: with n_out = 0 the bytes are those of mixq_gemm_i8_fused_bf16 (the same fp32 operations in the same order); with
+ * outlier columns the two differ in the tail's summation order (32x32x16 against 16x16x32), hence possibly in the last bit of y.  Pad
+ * columns of x_out / w_out (>= n_out, or >= *n_out_dev) may hold anything, NaN patterns included: they are masked.
+ *   mixq_gemm_i8_decode_bf16  layout MIXQ_X_PACKED | MIXQ_W_F16X64 (the image a bf16 layer keeps) or MIXQ_X_PACKED | MIXQ_W_PACKED: the
+ *                             same bytes from either.  K % 64 == 0.
+ *   mixq_gemm_i4_decode_bf16  layout MIXQ_X_PACKED | MIXQ_W_PACKED only: both operands nibble-packed in P16X64, K the logical depth,
+ *                             K % 128 == 0.
+ * MIXQ_ACT_NONE, MIXQ_ACT_SILU and MIXQ_ACT_SILU_MUL are served; there is no row-maximum side output, as in fp16.  Refusals, all before
+ * any launch, the earlier one answering where two coincide:
+ *   1 MIXQ_EINVAL  an unknown layout bit; MIXQ_XW_F6X128 at the int8 entry
+ *   2 MIXQ_ESHAPE  another layout than those above (plain operands, FP6 codes, fragment-order weights at the 4-bit entry or beside
+ *                  MIXQ_W_PACKED); MIXQ_ACT_SILU_PAIR; M > 32
+ *   3 MIXQ_EINVAL  M < 0, N < 0, K <= 0, n_out < 0; q_x, q_w, x_scale, scale_col or y NULL (when M > 0 and N > 0); an unknown act;
+ *                  MIXQ_ACT_SILU_MUL without its multiplier
+ *   4 MIXQ_ESHAPE  K % 64 (4-bit: K % 128), N % 4, ldy % 4, ldy < N
+ *   5 MIXQ_EINVAL  0 < lda < N
+ *   6 MIXQ_ESHAPE  outlier strides below the padded width or not multiples of 8
+ *   7 MIXQ_EINVAL  pointer alignment ("Alignment and strides")
+ *   8 MIXQ_EINVAL  a configuration forced with mixq_gemm_set_config other than "decode32" (the automatic values and decode32 itself
+ *                  run) - ahead of
+ *   9 MIXQ_OK      M == 0 or N == 0: nothing is launched.
+ * mixq_gemm_decode_pick_bf16(M, N, K, bit, layout): 1 exactly where the fp16 entry points' automatic plan takes the small-batch kernel
+ * for the same (bit, layout, M, N, K) - M <= 32, packed operands, K % 64 (4-bit: K % 128) == 0, N >= 4, and not the wide-layer exception
+ * (int8 fragment-order weights with N >= 8192, which the 32 x 64 tiling streams faster) - and the decode entry point of that width takes
+ * the layout; narrowed by measurement for nibbles: N >= 8192 answers 0 (a bf16 layer's other route there is the FP6 tiling, which is
+ * faster: profiles/decode_bf16.txt; the entry point itself still serves the shape); else 0.  MIXQ_EINVAL: M, N or K <= 0, bit not 4 or 8, a layout the fused entry points call a bad argument.
+ * mixq_linear_forward_decode_bf16(args, stream): mixq_linear_forward_bf16 with the small-batch GEMM - the `_bf16` quantise pass the block
+ * describes (plain, kept-map or known-maximum), then mixq_gemm_i8_decode_bf16 / mixq_gemm_i4_decode_bf16: bit-identical to those two
+ * calls.  qfmt MIXQ_FMT_P16X64; wfmt MIXQ_FMT_F16X64 or MIXQ_FMT_P16X64 for bit 8, MIXQ_FMT_P16X64 for bit 4.  After the NULL block, the
+ * bit and an unknown wfmt (MIXQ_EINVAL): another format, M > 32 or MIXQ_ACT_SILU_PAIR answer MIXQ_ESHAPE, then the pointer alignment
+ * MIXQ_EINVAL, before anything runs.  Only these: as with mixq_linear_forward_bf16, what the GEMM alone can refuse (K % 64 / K % 128, N % 4,
+ * ldy, lda, the outlier strides, a forced configuration other than decode32) is answered after the quantise pass has run - q_x, x_scale and
+ * x_out are then written and x's outlier columns zeroed.  mixq_version() still answers 1003; probe for the symbols. */
 
 /* ---- (i) per-token absmax + quantise ------------------------------------------------------------------
  * Replaces mixlib.FindRowScale(x, x_scale, M, K, bit) -> q_x   (linear.py:190-193, :221).
@@ -357,6 +402,20 @@ int mixq_gemm_i4_pair_bf16(const uint8_t* q_x, const uint8_t* q_w, const uint16_
                            const uint16_t* bias, uint16_t* y, int ldy, int M, int N, int K, int layout,
                            mixq_stream_t stream);
 int mixq_gemm_pair_supported_bf16(int M, int N, int K, int bit, int layout);
+/* "bf16 small-batch form (ABI 1.7)" above */
+int mixq_gemm_i8_decode_bf16(const int8_t* q_x, const int8_t* q_w, const uint16_t* x_scale,
+                             const uint16_t* scale_col, const uint16_t* x_out, int ldxo,
+                             const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
+                             const uint16_t* addend, int lda, const uint16_t* bias,
+                             uint16_t* y, int ldy, int M, int N, int K, int act, int layout,
+                             mixq_stream_t stream);
+int mixq_gemm_i4_decode_bf16(const uint8_t* q_x, const uint8_t* q_w, const uint16_t* x_scale,
+                             const uint16_t* scale_col, const uint16_t* x_out, int ldxo,
+                             const uint16_t* w_out, int ldwo, int n_out, const int32_t* n_out_dev,
+                             const uint16_t* addend, int lda, const uint16_t* bias,
+                             uint16_t* y, int ldy, int M, int N, int K, int act, int layout,
+                             mixq_stream_t stream);
+int mixq_gemm_decode_pick_bf16(int M, int N, int K, int bit, int layout);
 int mixq_quant_known_amax(uint16_t* x, const int32_t* ind, int n, const int32_t* n_dev, uint32_t* row_amax,
                           const uint32_t* col_mask, int map_words, uint16_t* x_scale, void* q, uint16_t* x_out, int32_t* flag,
                           int M, int K, int ldx, int ldo, int bit, float sigma, int qfmt, mixq_stream_t stream);
@@ -393,6 +452,8 @@ int mixq_linear_forward(const mixq_linear_args* args, mixq_stream_t stream);
 /* The same block with x, x_out, w_out, addend and y holding bfloat16 (x_scale, scale_col, bias fp16): the _bf16 quantise pass, then the
  * _bf16 GEMM; bit-identical to those two calls.  wfmt must be MIXQ_FMT_F16X64 or MIXQ_FMT_F6X128 (else MIXQ_ESHAPE, before anything runs). */
 int mixq_linear_forward_bf16(const mixq_linear_args* args, mixq_stream_t stream);
+/* ... and with the small-batch GEMM ("bf16 small-batch form (ABI 1.7)" above): M <= 32, wfmt F16X64 / P16X64 (bit 8), P16X64 (bit 4) */
+int mixq_linear_forward_decode_bf16(const mixq_linear_args* args, mixq_stream_t stream);
 
 /* ---- operand re-tiling ------------------------------------------------------------------------------------
  * Copy a plain [R,KB] byte matrix (int8 weights, or nibble-packed int4) into MIXQ_FMT_P16X64.

@@ -115,6 +115,14 @@ SIGNATURES.update({
 # ABI 1.6: the weight-only W8A16 layers in bfloat16 (x, addend, y bfloat16; the fp16 twins' argument lists)
 W8A16_BF16 = ("mixq_pack_w8a16_bf16", "mixq_gemm_w8a16_bf16", "mixq_gemm_w8a16_addend_bf16")
 SIGNATURES.update({name + "_bf16": SIGNATURES[name] for name in ("mixq_pack_w8a16", "mixq_gemm_w8a16", "mixq_gemm_w8a16_addend")})
+# ABI 1.7: the small-batch ("decode") kernel in bfloat16 (entry points of their own: what the `_bf16` GEMMs accept and choose is pinned)
+DECODE_BF16 = ("mixq_gemm_i8_decode_bf16", "mixq_gemm_i4_decode_bf16", "mixq_gemm_decode_pick_bf16", "mixq_linear_forward_decode_bf16")
+SIGNATURES.update({
+    "mixq_gemm_i8_decode_bf16": SIGNATURES["mixq_gemm_i8_fused_bf16"],
+    "mixq_gemm_i4_decode_bf16": SIGNATURES["mixq_gemm_i4_fused_bf16"],
+    "mixq_gemm_decode_pick_bf16": [_I, _I, _I, _I, _I],
+    "mixq_linear_forward_decode_bf16": SIGNATURES["mixq_linear_forward_bf16"],
+})
 RESTYPES = {"mixq_gemm_workspace_bytes": C.c_longlong}
 
 
@@ -168,7 +176,7 @@ def load():
         except AttributeError as e:
             if name in TUNING_ONLY:
                 continue                                   # the product library: no trace stamps, no tile-order knob
-            if name in PAIR_BF16 or name in W8A16_BF16:
+            if name in PAIR_BF16 or name in W8A16_BF16 or name in DECODE_BF16:
                 continue                                   # a library of an earlier ABI minor (mixq_version() does not tell): callers probe, mixlib.FusedLinear says so
             raise MixqBuildError(f"{LIB_PATH} does not export {name}; rebuild it") from e
         fn.argtypes = argtypes

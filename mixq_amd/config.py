@@ -63,6 +63,14 @@ class MixqConfig:
     # off ONLY because the ValueError for such a layer under a bfloat16 config is pinned behaviour; nothing else speaks against it.  Without
     # act_dtype=torch.bfloat16 the switch does nothing.  Not part of key(): it selects no GEMM plan and no joint image.
     w8a16_bf16: bool = False
+    # Opt-in to the small-batch ("decode") kernel in bfloat16 (mixq_gemm_i8_decode_bf16 / mixq_gemm_i4_decode_bf16, ABI 1.7): with
+    # act_dtype=torch.bfloat16 and decode_bf16=True a MixLinear_GEMM takes, at M <= 32, the route fp16 takes there - N / 32 workgroups x 8
+    # k-split waves instead of the 32 x 64 tiling's N / 64 workgroups - wherever mixq_gemm_decode_pick_bf16 answers 1 and no row maximum is
+    # asked of the GEMM; a 4-bit layer under small_batch_m4 > 0 then serves those batches from its nibble image.  The default is off because
+    # the route of a bf16 layer at small batch is observable behaviour of this ABI minor: with outlier columns the two routes differ in the
+    # tail's summation order, hence in bytes.  Without act_dtype=torch.bfloat16 the switch does nothing.  Not part of key(): it selects a route
+    # over images that already exist (a kept plan's identity carries it by itself: linear.py, _frozen_key).
+    decode_bf16: bool = False
 
     def __post_init__(self):
         if self.act_dtype not in (torch.float16, torch.bfloat16):

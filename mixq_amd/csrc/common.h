@@ -17,6 +17,7 @@ typedef float    f32x4  __attribute__((ext_vector_type(4)));
 typedef float    f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8  __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4  __attribute__((ext_vector_type(4)));
+typedef __bf16   bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4  __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2  __attribute__((ext_vector_type(2)));
 typedef u32x2 u32x2_u __attribute__((aligned(2)));   // fp16-aligned access to 4 halves
@@ -102,6 +103,14 @@ template <bool BF>
 __device__ __forceinline__ float a2f(uint16_t h) {
     if constexpr (BF) return __uint_as_float(static_cast<uint32_t>(h) << 16);
     else return h2f(h);
+}
+// Two fp32 values to one dword of the 16-bit container (lo in the low half), round-to-nearest-even: v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32.
+template <bool BF> __device__ __forceinline__ uint32_t mixq_cvt_pk(float lo, float hi) {
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    if constexpr (BF) return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
+    else return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{lo, hi}, f16x2));
 }
 // Maximum over the 64 lanes of a NON-NEGATIVE value, returned in every lane.  DPP moves inside the 16-lane rows (quad
 // swaps, half mirror, mirror: 4 VALU) and four v_readlane for the rows, instead of six ds_bpermute round trips.

@@ -892,6 +892,18 @@ bool forced_has_bf16(int wbit, int forced) { int c = -1; return cfg_family(force
 // (... that the `_pair_bf16` entry points can run: a tiling with the paired epilogue's bf16 form)
 bool forced_has_pair_bf16(int wbit, int forced) { int c = -1; return cfg_family(forced, &c) == ROUTE_WR && mixq_wr_has_pair_bf16(wbit, c); }
 
+// Where fp16's AUTOMATIC plan takes the small-batch kernel (gemm_skinny.hip): M <= 32 and packed operands (either packed weight layout) - a
+// weight stream, no LDS staging - except wide layers with fragment-order int8 weights, where the 32 x 64 weights-in-registers tiling streams
+// faster (gemm_wreg.hip).  One definition for plan_route below and for mixq_gemm_decode_pick_bf16.
+bool skinny_auto(int bit, int layout, int M, int N, int KB)
+{
+    if (layout == MIXQ_XW_F6X128) return false;
+    const bool wf16 = layout & MIXQ_W_F16X64;
+    const bool both_packed = (layout & MIXQ_X_PACKED) && ((layout & MIXQ_W_PACKED) || wf16);
+    if (wf16 && bit == 8 && N >= 8192) return false;
+    return mixq_skinny_applies(bit, M, N, KB, both_packed, both_packed);
+}
+
 // THE place where a route is decided: the fused entry points launch what this returns, the queries (mixq_gemm_pick_config_fmt,
 // mixq_gemm_pick_split[_bf16], mixq_gemm_amax_supported[_bf16]) read it with forced = -1.  `layout` is MIXQ_XW_F6X128 or a valid combination
 // of the flag bits (validate_fused), `act` decides the paired epilogue (and keeps the multiplier form off stream-K), `forced` is this device's
@@ -934,12 +946,10 @@ Route plan_route(int bit, int layout, int M, int N, int KB, int act, bool want_a
         if (forced == -1 && !pair) mixq_wr_split(6, M, N, KB, r.cfg, &r.n1, &r.cfg2);   // (a partial last round of tiles: two launches, as for int8 below)
         return r;
     }
-    // small-batch form (gemm_skinny.hip): M <= 32, packed operands (either packed layout): a weight stream, no LDS staging
+    // small-batch form (gemm_skinny.hip): the automatic rule is skinny_auto above; forced, wherever the kernel applies
     const bool both_packed = x_packed && (w_packed || wf16);
-    // (wide layers with fragment-order int8 weights: the 32 x 64 weights-in-registers tiling streams faster, gemm_wreg.hip)
-    const bool wide_wr = wf16 && bit == 8 && N >= 8192 && !is_forced;
     const bool forced_skinny = is_forced && fk == ROUTE_SKINNY;
-    if (!pair && !wide_wr && (!is_forced || forced_skinny) && mixq_skinny_applies(bit, M, N, KB, both_packed, both_packed)) {
+    if (!pair && (forced_skinny ? mixq_skinny_applies(bit, M, N, KB, both_packed, both_packed) : (!is_forced && skinny_auto(bit, layout, M, N, KB)))) {
         if (want_amax) return refuse(MIXQ_ESHAPE);               // the row-maximum side output lives in the weights-in-registers kernels
         return Route{MIXQ_OK, ROUTE_SKINNY, 0, 0, -1};
     }
@@ -1097,6 +1107,61 @@ extern "C" int mixq_gemm_i8_fused_amax_bf16(const int8_t* q_x, const int8_t* q_w
     if (!row_amax) return MIXQ_EINVAL;
     return gemm_fused({q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y, ldy, M, N, K, act,
                        row_amax, col_mask, true}, K, layout, 8, stream);
+}
+// ABI 1.7: the small-batch kernel in bfloat16 (include/mixq_hip.h, "bf16 small-batch form").  Entry points of their own: what the `_bf16` ones
+// above answer and write stays what it was.  Refusals in this order, all before any launch: the layout (a combination of flag bits the fused
+// entry points do not know: MIXQ_EINVAL; one this kernel does not read: MIXQ_ESHAPE), the paired act (MIXQ_ESHAPE), M > 32 (MIXQ_ESHAPE),
+// validate_fused's sizes / nulls / act / shape / stride / alignment checks, a forced configuration other than decode32 (MIXQ_EINVAL), then the
+// M == 0 || N == 0 early-out.
+namespace {
+int gemm_decode_bf16(MixqFusedProblem p, int K, int layout, int bit, mixq_stream_t stream)
+{
+    const bool f6 = layout == MIXQ_XW_F6X128;
+    if (f6 && bit != 4) return MIXQ_EINVAL;
+    if (!f6 && (layout & ~(MIXQ_X_PACKED | MIXQ_W_PACKED | MIXQ_W_F16X64))) return MIXQ_EINVAL;
+    const bool ok_layout = layout == (MIXQ_X_PACKED | MIXQ_W_PACKED) || (bit == 8 && layout == (MIXQ_X_PACKED | MIXQ_W_F16X64));
+    if (!ok_layout || p.act == MIXQ_ACT_SILU_PAIR || p.M > 32) return MIXQ_ESHAPE;
+    // the remaining checks are the fp16 container's (sizes, nulls, act and its operands, K / N / ldy shape, lda, outlier strides, alignment):
+    // the kernel is the fp16 one with another container, and validate_fused's bf16 branch speaks for the weights-in-registers kernels
+    p.bf16 = false;
+    if (int rc = validate_fused(p, K, layout, bit, -1)) return rc;
+    p.bf16 = true;
+    const int forced = g_forced_cfg.get();
+    if (forced >= 0) { int c = -1; if (cfg_family(forced, &c) != ROUTE_SKINNY) return MIXQ_EINVAL; }
+    if (p.M == 0 || p.N == 0) return MIXQ_OK;
+    if (!mixq_skinny_applies(bit, p.M, p.N, p.KB, true, true)) return MIXQ_ESHAPE;
+    return mixq_skinny_launch_bf16(p, bit, (layout & MIXQ_W_F16X64) ? 1 : 0, mixq_stream(stream));
+}
+}  // namespace
+extern "C" int mixq_gemm_i8_decode_bf16(const int8_t* q_x, const int8_t* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
+                                        const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out,
+                                        const int32_t* n_out_dev, const uint16_t* addend, int lda, const uint16_t* bias,
+                                        uint16_t* y, int ldy, int M, int N, int K, int act, int layout, mixq_stream_t stream)
+{
+    return gemm_decode_bf16({q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y, ldy, M, N, K, act,
+                             nullptr, nullptr, true}, K, layout, 8, stream);
+}
+extern "C" int mixq_gemm_i4_decode_bf16(const uint8_t* q_x, const uint8_t* q_w, const uint16_t* x_scale, const uint16_t* scale_col,
+                                        const uint16_t* x_out, int ldxo, const uint16_t* w_out, int ldwo, int n_out,
+                                        const int32_t* n_out_dev, const uint16_t* addend, int lda, const uint16_t* bias,
+                                        uint16_t* y, int ldy, int M, int N, int K, int act, int layout, mixq_stream_t stream)
+{
+    return gemm_decode_bf16({q_x, q_w, x_scale, scale_col, x_out, ldxo, w_out, ldwo, n_out, n_out_dev, addend, lda, bias, y, ldy, M, N, K / 2, act,
+                             nullptr, nullptr, true}, K, layout, 4, stream);
+}
+// 1 where fp16's automatic plan takes the small-batch kernel for the same (bit, layout, M, N, K) - skinny_auto, the definition plan_route
+// reads - except wide nibble layers (N >= 8192), where the bf16 alternative is not fp16's: a bf16 layer's other route is the FP6 tiling, and
+// at 4096 -> 11008 the nibble stream measured 11 - 14 % slower than it (profiles/decode_bf16.txt).  Else 0.  Bad arguments: MIXQ_EINVAL.
+extern "C" int mixq_gemm_decode_pick_bf16(int M, int N, int K, int bit, int layout)
+{
+    if (M <= 0 || N <= 0 || K <= 0 || (bit != 4 && bit != 8)) return MIXQ_EINVAL;
+    const bool f6 = layout == MIXQ_XW_F6X128;
+    if (f6 ? bit != 4 : (layout & ~(MIXQ_X_PACKED | MIXQ_W_PACKED | MIXQ_W_F16X64)) != 0) return MIXQ_EINVAL;
+    if (!f6 && (layout & MIXQ_W_F16X64) && layout != (MIXQ_X_PACKED | MIXQ_W_F16X64)) return MIXQ_EINVAL;
+    if ((bit == 4 && (K & 1)) || (N & 3)) return 0;
+    if (bit == 4 && layout != (MIXQ_X_PACKED | MIXQ_W_PACKED)) return 0;      // (mixq_gemm_i4_decode_bf16 reads nibbles in P16X64 only)
+    if (bit == 4 && N >= 8192) return 0;                                      // (measured slower than the FP6 route: see above)
+    return skinny_auto(bit, layout, M, N, bit == 8 ? K : K / 2) ? 1 : 0;
 }
 // ABI 1.5: the joint gate / up launch in bfloat16 (include/mixq_hip.h).  Entry points of their own - the `_bf16` ones above keep answering
 // MIXQ_ESHAPE for MIXQ_ACT_SILU_PAIR - without an act and an addend argument; N counts the interleaved rows, y is [M, N / 2].

@@ -15,6 +15,12 @@
 // weights incl. ~4 us of launch + reduction + epilogue; the stream itself runs at ~5 TB/s), 1.3-2.5x the tiled kernel.
 // A [N/32][K/64] block order (contiguous per-workgroup stream) and 2 workgroups per CU were tried: no difference.
 // Reference call sites replaced: mixlib.int8FusedDequantize[Silu] (modules/linear.py:235-283, :321-366) at small batch.
+//
+// The bfloat16 forms (x_out / w_out, addend and y in bfloat16; x_scale, scale_col and bias fp16 as ever: include/mixq_hip.h, "bf16 small-batch
+// form") are THIS file compiled a second time as gemm_skinny_bf16.hip (MIXQ_SKINNY_BF16_TU), the container a trailing template parameter there -
+// a translation unit and GPU code object of their own, as gemm_wreg_bf16.hip is for gemm_wreg.hip; in this file's own object BF is the constant
+// `false` and the two kernels keep the names and the instructions they had.  The k loop and the exact cross-wave sum are the same code; what
+// differs is the tail's MFMA (v_mfma_f32_32x32x16_bf16, whose lane maps are the f16 ones), the widening of the addend and the ONE rounding of y.
 #include "common.h"
 #include "gemm_skinny.h"
 #include <type_traits>
@@ -37,9 +43,21 @@ __device__ __forceinline__ float sk_silu(float v) { return mixq_silu(v); }   // 
 // UNROLL: k-steps whose loads are in flight together (x2 buffers); MINW: waves per SIMD the register budget must allow.
 // I4: both operands nibble-packed int4 (KB = K/2 bytes per row): every 16-byte fragment is expanded in registers to the
 // two int8 fragments 16*q of its even / odd columns (as gemm.hip does) and the factor 256 leaves in the epilogue.
-template <int UNROLL, int MINW, bool I4>
+// BF (the 16-bit container of x_out, w_out, addend and y) exists as a template parameter only where this file is compiled as
+// gemm_skinny_bf16.hip: here the kernels keep their three-argument names, and the fp16 code object the bytes it had.
+// (A macro and not a defaulted `bool BF = false`: a fourth template argument would change the fp16 kernels' mangled names, hence the .note
+// section and the symbol table of an object that is otherwise the parent's; gemm_w8a16.hip and gemm_wreg.hip do the same.)
+#ifdef MIXQ_SKINNY_BF16_TU
+#define MIXQ_SKINNY_BF_TPARAM , bool BF
+#else
+#define MIXQ_SKINNY_BF_TPARAM
+#endif
+template <int UNROLL, int MINW, bool I4 MIXQ_SKINNY_BF_TPARAM>
 __global__ __launch_bounds__(SKW * 64, MINW) void gemm_skinny_kernel(const SkinnyArgs a)
 {
+#ifndef MIXQ_SKINNY_BF16_TU
+    constexpr bool BF = false;
+#endif
     __shared__ __attribute__((aligned(16))) uint8_t lds[SKW * 4096];    // [wave][4 reg groups][64 lanes] x 16 B
     const int tid = threadIdx.x, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
     const int wave = wave_id_uniform();
@@ -146,6 +164,12 @@ __global__ __launch_bounds__(SKW * 64, MINW) void gemm_skinny_kernel(const Skinn
         o[0] = h2f(static_cast<uint16_t>(v.x & 0xffffu)); o[1] = h2f(static_cast<uint16_t>(v.x >> 16));
         o[2] = h2f(static_cast<uint16_t>(v.y & 0xffffu)); o[3] = h2f(static_cast<uint16_t>(v.y >> 16));
     };
+    auto unpack4a = [&](u32x2 v, float* o) {                            // the addend / multiplier: the activation container
+        if constexpr (BF) {
+            o[0] = a2f<true>(static_cast<uint16_t>(v.x & 0xffffu)); o[1] = a2f<true>(static_cast<uint16_t>(v.x >> 16));
+            o[2] = a2f<true>(static_cast<uint16_t>(v.y & 0xffffu)); o[3] = a2f<true>(static_cast<uint16_t>(v.y >> 16));
+        } else unpack4(v, o);
+    };
     const int m = lr;                                                   // this lane's token row
     const int mc = m < a.M ? m : a.M - 1;
     const float sxv = h2f(a.sx[mc]) * (I4 ? (1.f / 256.f) : 1.f);
@@ -176,7 +200,8 @@ __global__ __launch_bounds__(SKW * 64, MINW) void gemm_skinny_kernel(const Skinn
                     wq[d] &= keep; xq[d] &= keep;
                 }
             }
-            f = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wq), __builtin_bit_cast(f16x8, xq), f, 0, 0, 0);
+            if constexpr (BF) f = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wq), __builtin_bit_cast(bf16x8, xq), f, 0, 0, 0);
+            else f = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wq), __builtin_bit_cast(f16x8, xq), f, 0, 0, 0);
         }
     }
 #pragma unroll
@@ -186,7 +211,7 @@ __global__ __launch_bounds__(SKW * 64, MINW) void gemm_skinny_kernel(const Skinn
         float v[4] = {f[4 * g], f[4 * g + 1], f[4 * g + 2], f[4 * g + 3]};
         float av[4] = {0.f, 0.f, 0.f, 0.f};
         if (a.addend) {
-            unpack4(*reinterpret_cast<const u32x2_u*>(a.addend + static_cast<size_t>(mc) * a.lda + nc), av);
+            unpack4a(*reinterpret_cast<const u32x2_u*>(a.addend + static_cast<size_t>(mc) * a.lda + nc), av);
             if (a.act != MIXQ_ACT_SILU_MUL) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] += av[e];
@@ -208,8 +233,13 @@ __global__ __launch_bounds__(SKW * 64, MINW) void gemm_skinny_kernel(const Skinn
         }
         if (m < a.M && n < a.N) {
             u32x2 o;
-            o.x = static_cast<uint32_t>(f2h(v[0])) | (static_cast<uint32_t>(f2h(v[1])) << 16);
-            o.y = static_cast<uint32_t>(f2h(v[2])) | (static_cast<uint32_t>(f2h(v[3])) << 16);
+            if constexpr (BF) {                                         // ONE rounding, to nearest even: v_cvt_pk_bf16_f32
+                o.x = mixq_cvt_pk<true>(v[0], v[1]);
+                o.y = mixq_cvt_pk<true>(v[2], v[3]);
+            } else {
+                o.x = static_cast<uint32_t>(f2h(v[0])) | (static_cast<uint32_t>(f2h(v[1])) << 16);
+                o.y = static_cast<uint32_t>(f2h(v[2])) | (static_cast<uint32_t>(f2h(v[3])) << 16);
+            }
             *reinterpret_cast<u32x2_u*>(a.y + static_cast<size_t>(m) * a.ldy + n) = o;
         }
     }
@@ -217,12 +247,21 @@ __global__ __launch_bounds__(SKW * 64, MINW) void gemm_skinny_kernel(const Skinn
 
 }  // namespace
 
+#ifndef MIXQ_SKINNY_BF16_TU
 bool mixq_skinny_applies(int bit, int M, int N, int KB, bool x_packed, bool w_packed)
 {
     return (bit == 8 || bit == 4) && M >= 1 && M <= 32 && x_packed && w_packed && (KB % 64) == 0 && N >= 4;
 }
 
-int mixq_skinny_launch(const MixqFusedProblem& p, int bit, int wf16, hipStream_t st)
+#define MIXQ_SKINNY_LAUNCH mixq_skinny_launch
+#define MIXQ_SKINNY_KERNEL(I4) gemm_skinny_kernel<4, 2, I4>
+#else
+// (the bf16 unit: gemm_skinny_bf16.hip.  The same launch over the two bfloat16 instantiations)
+#define MIXQ_SKINNY_LAUNCH mixq_skinny_launch_bf16
+#define MIXQ_SKINNY_KERNEL(I4) gemm_skinny_kernel<4, 2, I4, true>
+#endif
+
+int MIXQ_SKINNY_LAUNCH(const MixqFusedProblem& p, int bit, int wf16, hipStream_t st)
 {
     const int M = p.M, N = p.N;
     SkinnyArgs a;
@@ -230,7 +269,7 @@ int mixq_skinny_launch(const MixqFusedProblem& p, int bit, int wf16, hipStream_t
     a.sx = p.x_scale; a.sw = p.scale_col; a.xo = p.x_out; a.wo = p.w_out; a.n_out_dev = p.n_out_dev; a.addend = p.addend; a.bias = p.bias; a.y = p.y;
     a.M = M; a.N = N; a.KB = p.KB; a.ldxo = p.ldxo; a.ldwo = p.ldwo; a.n_out = p.n_out; a.lda = p.lda; a.ldy = p.ldy; a.act = p.act;
     a.xrows16 = (M + 15) & ~15; a.wrows16 = (N + 15) & ~15; a.wf16 = wf16;
-    if (bit == 8) hipLaunchKernelGGL((gemm_skinny_kernel<4, 2, false>), dim3((N + 31) / 32), dim3(SKW * 64), 0, st, a);
-    else          hipLaunchKernelGGL((gemm_skinny_kernel<4, 2, true>), dim3((N + 31) / 32), dim3(SKW * 64), 0, st, a);
+    if (bit == 8) hipLaunchKernelGGL((MIXQ_SKINNY_KERNEL(false)), dim3((N + 31) / 32), dim3(SKW * 64), 0, st, a);
+    else          hipLaunchKernelGGL((MIXQ_SKINNY_KERNEL(true)), dim3((N + 31) / 32), dim3(SKW * 64), 0, st, a);
     return mixq_launch_status();
 }

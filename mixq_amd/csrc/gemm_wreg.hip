@@ -86,10 +86,7 @@ template <bool BF> __device__ __forceinline__ f32x4 wr_tail_mfma(u32x4 w, u32x4 
     if constexpr (BF) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(wr_bf16x8, w), __builtin_bit_cast(wr_bf16x8, x), c, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
 }
-template <bool BF> __device__ __forceinline__ uint32_t wr_cvt_pk(float lo, float hi) {   // round-to-nearest-even: v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32
-    if constexpr (BF) return __builtin_bit_cast(uint32_t, __builtin_convertvector(wr_f32x2{lo, hi}, wr_bf16x2));
-    else return __builtin_bit_cast(uint32_t, __builtin_convertvector(wr_f32x2{lo, hi}, wr_f16x2));
-}
+template <bool BF> __device__ __forceinline__ uint32_t wr_cvt_pk(float lo, float hi) { return mixq_cvt_pk<BF>(lo, hi); }   // (common.h: shared with gemm_skinny.hip)
 
 // compile-time loop: f(std::integral_constant<int, I>{}) for I in [I0, N) (ring slots are compile-time registers)
 template <int I, int N, class F> __device__ __forceinline__ void wr_static_for(F&& f) {

@@ -456,7 +456,13 @@ class MixLinear_GEMM(nn.Module):
         return FMT_R6X128 if _fmt_of(wpk) == FMT_F6X128 else FMT_P16X64
 
     def _small_batch_image(self, M):
-        return self.bit == 4 and M is not None and 0 < M <= self.config.small_batch_m4 and self.config.pack_fmt4 == FMT_F6X128 and not self.weight_only
+        small = self.bit == 4 and M is not None and 0 < M <= self.config.small_batch_m4 and self.config.pack_fmt4 == FMT_F6X128 and not self.weight_only
+        if small and self.act_dtype == torch.bfloat16 and self.config.decode_bf16:
+            # a bfloat16 model under decode_bf16: the nibble image serves the batches the small-batch form is picked for, the FP6 image the
+            # rest (wide layers, M > 32).  Without the flag nothing changes: the nibble image reaches the `_bf16` GEMM, which refuses it.
+            pick = getattr(_backend, "decode_pick", None)
+            return pick is not None and bool(pick(M, self.out_features, self.in_features, 4, FMT_P16X64, FMT_P16X64))
+        return small
 
     def _packed_small(self):
         """The nibble (P16X64) image of a 4-bit layer, for small batches; made from the plain matrix while it exists, from the FP6 image after."""
@@ -570,6 +576,15 @@ class MixLinear_GEMM(nn.Module):
             self._wo_ready, self._wo_key = _gemm_ready(wc if wc.dtype == dt else wc.to(dt)), key
         return self._wo_ready
 
+    def _decode_applies(self, M, w, row_amax=None):
+        """ONE predicate for both routes (_gemm: two calls; _build_plan: one call): this GEMM of M rows over the weight image `w` takes the
+        small-batch form in bfloat16 (MixqConfig.decode_bf16; mixq_gemm_i8_decode_bf16 / mixq_gemm_i4_decode_bf16).  Read from the config on
+        every call: a flip of the flag on a live layer takes effect at the next forward (_frozen_key carries it)."""
+        if self.act_dtype != torch.bfloat16 or not self.config.decode_bf16 or self.weight_only or row_amax is not None or w is None:
+            return False
+        pick = getattr(_backend, "decode_pick", None)        # (a backend without the query has no small-batch form: it never sees `decode`)
+        return pick is not None and bool(pick(M, self.out_features, self.in_features, self.bit, self.x_fmt(M), _fmt_of(w)))
+
     def _gemm(self, cache, M, act, addend=None, row_amax=None, col_mask=None):
         n = int(self.ind.shape[0])
         xo = wo = n_dev = None
@@ -603,6 +618,8 @@ class MixLinear_GEMM(nn.Module):
         extra = {} if row_amax is None else {"row_amax": row_amax, "col_mask": col_mask}
         if self.act_dtype != torch.float16:
             extra["dtype"] = self.act_dtype                  # (the _bf16 entry points: y, x_out, w_out and the addend in bfloat16)
+            if self._decode_applies(M, wpk, row_amax):
+                extra["decode"] = True                       # (handed on only where it holds: a backend without the argument never sees it)
         if n:
             return _backend.FusedLinear(qx, w, cache.x_scale, self.scale_col, _wide(xo, n_cap), _wide(wo, n_cap), n_cap, self.bias, M, self.out_features, self.in_features, bit=self.bit,
                                         act=act, addend=addend, n_out_dev=n_dev, **extra)
@@ -640,7 +657,7 @@ class MixLinear_GEMM(nn.Module):
         dd = d["_d"]
         return (M, inputs.stride(0), inputs.device, id(cache), id(cache.x_scale), id(ind), ind._version, id(dd.wpk), id(dd.wpk_small), id(qw),
                 -1 if qw is None else qw._version, id(wc), -1 if wc is None else wc._version, id(b.get("bias", d.get("bias"))),
-                id(b.get("scale_col"))) + d["config"].key()
+                id(b.get("scale_col"))) + d["config"].key() + (bool(d["config"].decode_bf16),)   # (a route over the same images: not in key(), but the kept block's entry point)
 
     def _build_plan(self, cache, inputs, M):
         if M == 0 or inputs.dtype != self.act_dtype or inputs.stride(1) != 1 or inputs.stride(0) % 8:
@@ -658,6 +675,8 @@ class MixLinear_GEMM(nn.Module):
             wo = _wide(wo, _pad16(n))
         # (frozen: `ind` never changes again, so the quantise pass gets the kept bit mask of its columns instead of building one per launch)
         extra = {} if self.act_dtype == torch.float16 else {"dtype": self.act_dtype}      # (mixq_linear_forward_bf16)
+        if self._decode_applies(M, wpk):
+            extra["decode"] = True                           # (mixq_linear_forward_decode_bf16)
         return _backend.ForwardPlan(M, self.out_features, self.in_features, self.bit, self._sigma_f, inputs.stride(0), ind_buf, n, n_dev,
                                     cache.x_scale, wpk, self.scale_col, wo, self.bias, self.x_fmt(M), kept_mask=self._col_mask() if n else None, **extra)
 

@@ -802,6 +802,27 @@ def _pair_bf16_entry(name):
     return fn
 
 
+def _decode_bf16_entry(name, who="FusedLinear"):
+    """An ABI 1.7 entry point of the loaded library (the small-batch kernel in bfloat16), probed by symbol like the ABI 1.5 ones: a library
+    built before it says so here, by name - nothing falls back to the other route."""
+    fn = getattr(_capi.load(), name, None)
+    if fn is None:
+        raise RuntimeError(f"{who}: the loaded library ({_capi.LIB_PATH}) does not export {name} (ABI 1.7, the small-batch form in "
+                           f"bfloat16); rebuild it")
+    return fn
+
+
+def decode_pick(M, N, K, bit, x_fmt, w_fmt):
+    """True where the small-batch ("decode") kernel is the route of choice for a bfloat16 problem (mixq_gemm_decode_pick_bf16: exactly where
+    the fp16 entry points' automatic plan takes it) and FusedLinear(..., decode=True) / ForwardPlan(..., decode=True) serve it."""
+    if x_fmt != FMT_P16X64 or w_fmt not in (FMT_P16X64, FMT_F16X64):
+        return False
+    rc = _decode_bf16_entry("mixq_gemm_decode_pick_bf16", "decode_pick")(M, N, K, bit, _layout_bits(x_fmt, w_fmt))
+    if rc < 0:
+        raise _capi.MixqError("mixq_gemm_decode_pick_bf16", rc)
+    return rc == 1
+
+
 def _check_same_dtype(dtype, who, **tensors):
     """The 16-bit tensors of a GEMM call (x_out, w_out, addend, out) share ONE container, the layer's: no mixing, no silent conversion."""
     for name, t in tensors.items():
@@ -819,7 +840,7 @@ def amax_supported(M, N, K, x_fmt, w_fmt, dtype=torch.float16):
 
 
 def FusedLinear(q_x, q_w, x_scale, scale_col, x_out, w_out, n_out, bias, M, N, K, bit=8, act=ACT_NONE, n_out_dev=None,
-                addend=None, out=None, x_packed=None, w_packed=None, row_amax=None, col_mask=None, dtype=torch.float16):
+                addend=None, out=None, x_packed=None, w_packed=None, row_amax=None, col_mask=None, dtype=torch.float16, decode=False):
     """(iii)+(iv): int8/int4 MFMA GEMM + dequant + fp16 outlier correction + addend + act + bias -> fp16 [M,N].
     `dtype` (float16, or bfloat16: the `_bf16` entry points; ACT_SILU_PAIR in bfloat16: the `_pair_bf16` ones, ABI 1.5 - a library without
     them is a RuntimeError naming the symbol) is the container of x_out, w_out, addend and y - with no outlier columns, no
@@ -830,7 +851,17 @@ def FusedLinear(q_x, q_w, x_scale, scale_col, x_out, w_out, n_out, bias, M, N, K
     outlier count: n_out then is the capacity of x_out / w_out (columns >= the device count are ignored, whatever they hold).
     `row_amax` (device int32 [>= M], zero on entry): also maximise, per row, the fp16 bit patterns |y| over the columns whose bit in
     `col_mask` (int32 words, bit n) is clear - the next layer's pre-pass maximum (mixq_gemm_i8_fused_amax; int8, fragment-order
-    weights only)."""
+    weights only).
+    `decode` (bfloat16 only, M <= 32): the small-batch kernel, mixq_gemm_i8_decode_bf16 / mixq_gemm_i4_decode_bf16 (ABI 1.7; ask decode_pick
+    where it is the route of choice).  It has no row-maximum side output and no paired form, and fp16 takes the kernel by itself."""
+    if decode:
+        why = ("dtype=float16 takes the small-batch kernel by itself (the automatic route of mixq_gemm_i8_fused)" if dtype != torch.bfloat16
+               else "the small-batch kernel has no row-maximum side output" if row_amax is not None
+               else "the small-batch kernel has no paired gate / up form (ACT_SILU_PAIR)" if act == ACT_SILU_PAIR else None)
+        if why:
+            raise RuntimeError(f"FusedLinear: decode=True: {why}")
+        fn_decode_name = "mixq_gemm_i8_decode_bf16" if bit == 8 else "mixq_gemm_i4_decode_bf16"
+        fn_decode = _decode_bf16_entry(fn_decode_name)
     _dev_check(q_x, q_w, x_scale, scale_col, row_amax, col_mask)
     if x_scale.numel() < M or scale_col.numel() < N:
         raise RuntimeError("FusedLinear: x_scale / scale_col are shorter than M / N")
@@ -884,6 +915,12 @@ def FusedLinear(q_x, q_w, x_scale, scale_col, x_out, w_out, n_out, bias, M, N, K
                    n_out, _ptr(n_out_dev), ap, lda, _ptr(bias), y.data_ptr(), y.stride(0), M, N, K, act, _layout_bits(x_fmt, w_fmt),
                    row_amax.data_ptr(), _ptr(col_mask), _stream())
         return y
+    if decode:
+        rc = fn_decode(q_x.data_ptr(), q_w.data_ptr(), x_scale.data_ptr(), scale_col.data_ptr(), xop, ldxo, wop, ldwo, n_out,
+                       _ptr(n_out_dev), ap, lda, _ptr(bias), y.data_ptr(), y.stride(0), M, N, K, act, _layout_bits(x_fmt, w_fmt), _stream())
+        if rc != 0:
+            raise _capi.MixqError(fn_decode_name, rc)
+        return y
     fn = ("mixq_gemm_i8_fused" if bit == 8 else "mixq_gemm_i4_fused") + sfx
     _capi.call(fn, q_x.data_ptr(), q_w.data_ptr(), x_scale.data_ptr(), scale_col.data_ptr(), xop, ldxo, wop, ldwo, n_out,
                _ptr(n_out_dev), ap, lda, _ptr(bias), y.data_ptr(), y.stride(0), M, N, K, act, _layout_bits(x_fmt, w_fmt), _stream())
@@ -895,12 +932,21 @@ class ForwardPlan:
     a forward then costs three allocations, four pointer updates and ONE foreign call that enqueues the quantise pass and the
     GEMM (the steady state of linear.py:187-193 + :244-285).  Holds references to every tensor whose address it carries."""
 
-    __slots__ = ("args", "ref", "fn", "keep", "M", "N", "K", "ldx", "n", "ldxo", "q_shape", "q_dtype", "qfmt", "device", "lock", "captured", "kept_mask", "dtype", "fn_name")
+    __slots__ = ("args", "ref", "fn", "keep", "M", "N", "K", "ldx", "n", "ldxo", "q_shape", "q_dtype", "qfmt", "device", "lock", "captured", "kept_mask", "dtype", "fn_name", "decode")
 
-    def __init__(self, M, N, K, bit, sigma, ldx, ind_buf, n, n_dev, x_scale, q_w, scale_col, w_out, bias, qfmt, act=ACT_NONE, kept_mask=None, dtype=torch.float16):
+    def __init__(self, M, N, K, bit, sigma, ldx, ind_buf, n, n_dev, x_scale, q_w, scale_col, w_out, bias, qfmt, act=ACT_NONE, kept_mask=None, dtype=torch.float16, decode=False):
         import ctypes as C
         # dtype: the container of x, x_out, w_out and y (float16, or bfloat16: mixq_linear_forward_bf16); checked against x on every run
         self.dtype, self.fn_name = dtype, "mixq_linear_forward" + _act_suffix(dtype, "ForwardPlan")
+        # decode (bfloat16, M <= 32): the small-batch GEMM behind the same block, mixq_linear_forward_decode_bf16 (ABI 1.7)
+        self.decode = bool(decode)
+        if decode:
+            why = ("dtype=float16 takes the small-batch kernel by itself (the automatic route of mixq_linear_forward)" if dtype != torch.bfloat16
+                   else "the small-batch kernel has no paired gate / up form (ACT_SILU_PAIR)" if act == ACT_SILU_PAIR else None)
+            if why:
+                raise RuntimeError(f"ForwardPlan: decode=True: {why}")
+            self.fn_name = "mixq_linear_forward_decode_bf16"
+            _decode_bf16_entry(self.fn_name, "ForwardPlan")
         _dev_check(x_scale, q_w, scale_col, ind_buf, n_dev, w_out, bias)
         if x_scale.numel() < M or scale_col.numel() < N:
             raise RuntimeError("ForwardPlan: x_scale / scale_col are shorter than M / N")

@@ -15,7 +15,13 @@ columns.  Prints one JSON line: per dtype the us per forward of every round, the
                off: float16 as the model runs it (joint), float16 with joint_gate_up=False, bfloat16 as a fused_bf16 model runs it (the two
                launches), and bfloat16 with joint_gate_up_bf16=True (mixq_gemm_i8_pair_bf16 / mixq_gemm_i4_pair_bf16)
 One JSON line: per form the us per call of every round, median, min, max; and what the joint launch saves in either dtype beside the
-spread of the bfloat16 two-launch rounds."""
+spread of the bfloat16 two-launch rounds.
+--decode: MixqConfig.decode_bf16 off against on, the frozen bfloat16 forward (one call: quantise pass + GEMM) at M in {1, 16, 32} with
+  HBM-COLD weights as tools/time_decode.py arranges them for float16: the launches of one hipGraph rotate through enough copies of the layer
+  to exceed the 256 MB MALL, twice.  4096 -> 4096 and 11008 -> 4096 (the narrow layers of a Llama-7B block), W8 and W4 (flag on: the nibble
+  image, small_batch_m4 = 32; flag off: the FP6 image), and 4096 -> 11008 as the control, where both configurations run the same kernel
+  ("entry" in the output names the one-call entry point that ran).  Flag-off and flag-on rounds ALTERNATE on one box; flag off is the route (and the code object) of a library without the flag.  One
+  JSON line per shape: per M the us per forward of every round, median, min, max, the off rounds' spread and on / off."""
 import argparse
 import json
 import os
@@ -166,6 +172,73 @@ def block_mode(args, device, side):
     print(json.dumps(out))
 
 
+def build_decode(device, K, N, bit, copies):
+    """`copies` frozen bfloat16 layers K -> N over ONE shared config (the flag is flipped on it), and the outlier columns of the batch."""
+    import copy
+    cfg = MixqConfig(act_dtype=torch.bfloat16)
+    cache = MixLibCache(32, sigma=bench.SIGMA, bit=bit, device=device, config=cfg)
+    torch.manual_seed(0)
+    kw = {}
+    if bit == 4:
+        scales = torch.ones(K) + torch.arange(K) * 1e-6
+        cols = bench.outlier_columns(K)
+        scales[cols] = 20.0 + torch.arange(cols.numel()) * 1e-3
+        kw["layer_scales"] = scales
+    first = MixLinear_GEMM.from_linear(torch.nn.Linear(K, N, bias=False).to(torch.bfloat16), bit, cache=cache, dev=device, **kw)
+    _, base, _ = bench.make_batches(1, 32, device, 0, Kc=K)
+    base = base.to(torch.bfloat16)
+    for _ in range(3):
+        first(base.clone(), None, True)
+    torch.cuda.synchronize()
+    assert first.add_outliers is False
+    layers = [first] + [copy.deepcopy(first) for _ in range(copies - 1)]
+    for l in layers:
+        l.cache = cache
+        l.config = cfg
+    return layers, cfg, base
+
+
+def decode_mode(args, device, side):
+    shapes = [(4096, 4096), (11008, 4096), (4096, 11008)]
+    for K, N in shapes:
+        for bit in (8, 4):
+            image = K * N * (1.0 if bit == 8 else 0.5)
+            copies = max(2, int(300e6 // image) + 1)                         # > 256 MB of weights per pass through the graph
+            layers, cfg, base = build_decode(device, K, N, bit, copies)
+            steps = 2 * copies
+            out = {"what": f"--decode: frozen bfloat16 MixLinear_GEMM W{bit}A{bit}O16 forward {K} -> {N}, {int(layers[0].ind.numel())} outlier columns, hipGraph of "
+                           f"{steps} forwards over {copies} copies of the layer (HBM-cold weights), median of {args.replays} replays per round, {args.rounds} "
+                           f"alternating rounds", "K": K, "N": N, "bit": bit, "device": _capi.device_info()}
+            for M in (1, 16, 32):
+                x0 = base[:M].contiguous()
+                bx = x0.unsqueeze(0).repeat(steps, 1, 1).contiguous()
+                restore = lambda bx=bx, x0=x0: bx.copy_(x0.unsqueeze(0).expand_as(bx))
+                graphs, route = {}, {}
+                for name, flag in (("off", False), ("on", True)):
+                    cfg.decode_bf16 = flag
+                    cfg.small_batch_m4 = 32 if (flag and bit == 4) else 0     # (flag off: a bf16 layer has no nibble route)
+                    graphs[name] = _capture(lambda i: layers[i % copies](bx[i], None, True), steps, side, warm=copies)
+                    route[name] = layers[0]._plan.fn_name
+                    restore()
+                us = {"off": [], "on": []}
+                for _ in range(args.rounds):
+                    for name in ("off", "on"):
+                        ms, _, _ = bench.conditioned_replay(graphs[name], side, restore=restore, replays=args.replays)
+                        us[name].append(round(ms * 1e3 / steps, 3))
+                r = {}
+                for name in ("off", "on"):
+                    v = sorted(us[name])
+                    r[name] = {"entry": route[name], "us_per_forward_rounds": us[name], "median_us": bench.median(v), "min_us": v[0], "max_us": v[-1]}
+                r["off_spread_us"] = round(r["off"]["max_us"] - r["off"]["min_us"], 3)
+                r["on_over_off"] = round(r["on"]["median_us"] / r["off"]["median_us"], 4)
+                out[f"M{M}"] = r
+                del graphs
+            cfg.decode_bf16, cfg.small_batch_m4 = False, 0
+            print(json.dumps(out), flush=True)
+            del layers
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bit", type=int, choices=[8, 4], default=8)
@@ -175,6 +248,7 @@ def main():
     ap.add_argument("--batch", type=int, default=bench.M)
     ap.add_argument("--once", choices=["fp16", "bf16", "block_fp16", "block_fp16_two_launch", "block_bf16", "block_bf16_joint"], default=None)
     ap.add_argument("--block", action="store_true", help="time the fused norm + quantise pass and the norm -> MLP block, bf16 against fp16")
+    ap.add_argument("--decode", action="store_true", help="time MixqConfig.decode_bf16 off against on at M in {1, 16, 32}, HBM-cold weights")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_bf16.py needs an MI355X")
@@ -191,6 +265,8 @@ def main():
         torch.cuda.synchronize()
         print(f"{args.once}: 50 replays of {args.steps} block calls, joint gate / up launch: {f[3]}")
         return
+    if args.decode:
+        return decode_mode(args, device, side)
     if args.block:
         return block_mode(args, device, side)
     dtypes = {"fp16": torch.float16, "bf16": torch.bfloat16}
