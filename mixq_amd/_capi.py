@@ -124,6 +124,11 @@ SIGNATURES.update({
     "mixq_linear_forward_decode_bf16": SIGNATURES["mixq_linear_forward_bf16"],
 })
 RESTYPES = {"mixq_gemm_workspace_bytes": C.c_longlong}
+# what `entry` says for an optional symbol (mixq_version() does not tell the ABI minors apart: the symbol itself is probed) that the loaded
+# library lacks - by name, nothing falls back to another route
+_MISSING = {name: "{who}: the loaded library ({lib}) does not export {name} (" + what + "); rebuild it" for names, what in (
+    (PAIR_BF16, "ABI 1.5, the joint gate / up launch in bfloat16"), (DECODE_BF16, "ABI 1.7, the small-batch form in bfloat16")) for name in names}
+_MISSING.update({name: "mixq_amd.mixlib: {lib} does not export {name} (the bfloat16 weight-only GEMM, ABI 1.6); rebuild it" for name in W8A16_BF16})
 
 
 class LinearArgs(C.Structure):
@@ -185,9 +190,18 @@ def load():
     return lib
 
 
+def entry(name: str, who: str = "FusedLinear"):
+    """The entry point `name` of the loaded library.  An optional one (PAIR_BF16 / W8A16_BF16 / DECODE_BF16) that a library of an earlier
+    ABI minor lacks is a RuntimeError that names it."""
+    fn = getattr(load(), name, None) if name in _MISSING else getattr(load(), name)
+    if fn is None:
+        raise RuntimeError(_MISSING[name].format(who=who, lib=LIB_PATH, name=name))
+    return fn
+
+
 def call(name: str, *args) -> None:
     """Call an entry point and raise MixqError on a non-zero status."""
-    rc = getattr(load(), name)(*args)
+    rc = entry(name)(*args)
     if rc != 0:
         raise MixqError(name, rc)
 

@@ -15,6 +15,7 @@ from . import linear as _L
 from . import mixlib as _hip_mixlib
 
 _backend = _hip_mixlib
+_PAIR_FMT = {8: _L.FMT_F16X64, 4: _L.FMT_F6X128}       # the images the paired epilogue reads: fragment-order int8, int4 as FP6 codes
 # (the switches of rounds 1-4 - FUSE_DOWN_AMAX, JOINT_GATE_UP, NORM_KEPT_MASK - are fields of the model's MixqConfig now: config.py)
 
 
@@ -86,7 +87,7 @@ class FasterTransformerRMSNorm(nn.Module):
         _refuse_bf16(config, "FasterTransformerRMSNorm")
         dtype = torch.bfloat16 if _is_bf16(config) else torch.float16
         if x.dtype != dtype:
-            raise RuntimeError(f"FasterTransformerRMSNorm: x must be {str(dtype).replace('torch.', '')} like the model's activations "
+            raise RuntimeError(f"FasterTransformerRMSNorm: x must be {_L._dtype_name(dtype)} like the model's activations "
                                f"(MixqConfig.act_dtype), got {x.dtype}")
         weight = self._operand(dtype)
         output = torch.empty_like(x)
@@ -164,8 +165,7 @@ class MixLlamaMLP(nn.Module):
             return False                                     # (bfloat16: the joint launch is an opt-in of its own, config.py; else the two launches below)
         if up.bit != gate.bit or up.weight_only or gate.weight_only or up.add_outliers:
             return False
-        # the kernels with the paired epilogue: int8 on fragment-order weights, int4 as FP6 codes (the default image of either width)
-        if (self.config.pack_fmt != _L.FMT_F16X64) if up.bit == 8 else (self.config.pack_fmt4 != _L.FMT_F6X128):
+        if _L._image_fmt(self.config, up.bit) != _PAIR_FMT[up.bit]:      # (the default image of either width)
             return False
         if up.in_features % (64 if up.bit == 8 else 128) or up.out_features % 8 or \
                 (up.in_features, up.out_features) != (gate.in_features, gate.out_features):
@@ -204,7 +204,7 @@ class MixLlamaMLP(nn.Module):
             return j
         up, gate = self.up_proj_, self.gate_proj_
         N, n = up.out_features, int(up.ind.shape[0])
-        wpk = _backend.PackOperand(interleave_pair_rows(up.q_weight, gate.q_weight), _L.FMT_F16X64 if up.bit == 8 else _L.FMT_F6X128)
+        wpk = _backend.PackOperand(interleave_pair_rows(up.q_weight, gate.q_weight), _PAIR_FMT[up.bit])
         scale = interleave_pair_rows(up.scale_col.reshape(-1), gate.scale_col.reshape(-1)).reshape(1, -1)
         bias = None
         if up.bias is not None or gate.bias is not None:
@@ -293,8 +293,7 @@ class MixLlamaMLP(nn.Module):
             xo, wo = _L._wide(xo, n_cap), _L._wide(wo, n_cap)
         extra = {}
         target = None
-        # (the container is said only where it is not float16, as MixLinear_GEMM._gemm does: another backend keeps the reference's argument lists)
-        dt = {} if self.config.act_dtype == torch.float16 else {"dtype": self.config.act_dtype}
+        dt = _L._container_kw(self.config.act_dtype)
         if self.config.fuse_down_amax and up.bit == 8 and down.bit == 8 and down.in_features == N and \
                 _backend.amax_supported(M, 2 * N, K, _L.FMT_P16X64, _L.FMT_F16X64, **dt):
             target = down.amax_target(M, x.device)

@@ -66,8 +66,12 @@ def unpack_int8_to_int4(weight: Tensor, ind: Tensor) -> Tensor:
     return _backend.unpack_int4_to_fp16(weight, ind)
 
 
-def _pad16(n: int) -> int:
-    return (n + 15) // 16 * 16
+_pad16, _dtype_name, _container_kw = _hip_mixlib._pad16, _hip_mixlib._dtype_name, _hip_mixlib._container_kw
+
+
+def _image_fmt(config, bit):
+    """The packed layout a layer of `bit` bits keeps its weights in under `config` (config.py: pack_fmt / pack_fmt4)."""
+    return config.pack_fmt if bit == 8 else config.pack_fmt4
 
 
 class _ColStore:
@@ -329,20 +333,24 @@ class MixLinear_GEMM(nn.Module):
         n = int(count.item())
         return ind_buf[:n].clone()
 
-    def _append_outliers(self, cache, inputs, ind):
-        """linear.py:205-221: pull the new columns out of x, dequantise the matching weight columns, append both."""
-        activation_outliers = _backend.ExtractOutliersAndSetToZeros(ind, inputs)
+    def _take_weight_cols(self, ind):
+        """Dequantise the weight columns `ind` and append them to `weight_cache` (linear.py:207-221)."""
         weight_cache = _backend.DequantWeightCols(self.q_weight, self.scale_col, ind, self.bit)
         if self._wstore is None:
             self._wstore = _ColStore(self.out_features, weight_cache.device,
                                      self.weight_cache if (self.weight_cache is not None and self.ind.shape[0]) else None)
+        self._wstore.append(weight_cache)
+        self.weight_cache = self._wstore.view() if self._wstore.n else weight_cache
+
+    def _append_outliers(self, cache, inputs, ind):
+        """linear.py:205-221: pull the new columns out of x, dequantise the matching weight columns, append both."""
+        activation_outliers = _backend.ExtractOutliersAndSetToZeros(ind, inputs)
+        self._take_weight_cols(ind)
         xs = _ColStore(inputs.shape[0], inputs.device,
                        cache.activation_outliers if (self.ind.shape[0] and cache.activation_outliers is not None) else None,
                        dtype=activation_outliers.dtype)
         xs.append(activation_outliers)
-        self._wstore.append(weight_cache)
         cache.activation_outliers = xs.view() if xs.n else activation_outliers
-        self.weight_cache = self._wstore.view() if self._wstore.n else weight_cache
         self.ind = torch.hstack((self.ind, ind))
         cache.ind = self.ind
 
@@ -489,13 +497,13 @@ class MixLinear_GEMM(nn.Module):
         if qw is None:
             if self._wpk is None and self._d.joint is not None:
                 # the layer is used on its own again (its MLP block took the joint route before): its own image, from the joint one
-                self._wpk = _backend.PackOperand(self._plain_weight(), self.config.pack_fmt if self.bit == 8 else self.config.pack_fmt4)
+                self._wpk = _backend.PackOperand(self._plain_weight(), _image_fmt(self.config, self.bit))
             return self._wpk                                             # compacted: the packed image is all there is
         if qw.shape[1] % 64:
             return None                                                  # (plain operands: the LDS-staged kernel's own loads)
         # W4A4: FP6 codes for the FP6 matrix pipe (config.pack_fmt4); as nibbles it stays with the LDS-staged kernel (P16X64 weights), whose
         # nibble expansion hides behind 32-cycle MFMAs, not behind the 16-cycle ones of the weights-in-registers kernel (28.0 vs 32.4 us)
-        fmt = self.config.pack_fmt if self.bit == 8 else self.config.pack_fmt4
+        fmt = _image_fmt(self.config, self.bit)
         key = (id(qw), qw.data_ptr(), qw._version, fmt)
         if self._wpk is None or self._wpk_key != key:
             self._wpk = _backend.PackOperand(qw, fmt)
@@ -588,7 +596,6 @@ class MixLinear_GEMM(nn.Module):
     def _gemm(self, cache, M, act, addend=None, row_amax=None, col_mask=None):
         n = int(self.ind.shape[0])
         xo = wo = n_dev = None
-        cap = 0
         if n:
             xo = cache.activation_outliers
             if xo is None or xo.shape[1] != n:
@@ -616,15 +623,13 @@ class MixLinear_GEMM(nn.Module):
             if want != FMT_PLAIN:
                 qx = _backend.PackOperand(qx[:M].contiguous(), want)
         extra = {} if row_amax is None else {"row_amax": row_amax, "col_mask": col_mask}
-        if self.act_dtype != torch.float16:
-            extra["dtype"] = self.act_dtype                  # (the _bf16 entry points: y, x_out, w_out and the addend in bfloat16)
-            if self._decode_applies(M, wpk, row_amax):
-                extra["decode"] = True                       # (handed on only where it holds: a backend without the argument never sees it)
+        extra.update(_container_kw(self.act_dtype))          # (y, x_out, w_out and the addend in bfloat16)
+        if self.act_dtype != torch.float16 and self._decode_applies(M, wpk, row_amax):
+            extra["decode"] = True                           # (handed on only where it holds: a backend without the argument never sees it)
         if n:
-            return _backend.FusedLinear(qx, w, cache.x_scale, self.scale_col, _wide(xo, n_cap), _wide(wo, n_cap), n_cap, self.bias, M, self.out_features, self.in_features, bit=self.bit,
-                                        act=act, addend=addend, n_out_dev=n_dev, **extra)
-        return _backend.FusedLinear(qx, w, cache.x_scale, self.scale_col, None, None, 0, self.bias, M, self.out_features,
-                                    self.in_features, bit=self.bit, act=act, addend=addend, **extra)
+            extra["n_out_dev"] = n_dev
+        tail = (_wide(xo, n_cap), _wide(wo, n_cap), n_cap) if n else (None, None, 0)
+        return _backend.FusedLinear(qx, w, cache.x_scale, self.scale_col, *tail, self.bias, M, self.out_features, self.in_features, bit=self.bit, act=act, addend=addend, **extra)
 
     def __getstate__(self):
         """copy.deepcopy / pickle of a frozen layer: the kept argument block of the one-call forward is a ctypes structure full of device
@@ -636,7 +641,7 @@ class MixLinear_GEMM(nn.Module):
         d.plan, d.plan_key, d.plans, d.retired = None, None, {}, []
         if d.joint is not None:                              # (the copy stands alone: its own image instead of a reference into the MLP block's)
             if d.wpk is None and self._buffers.get("q_weight") is None:
-                d.wpk = _backend.PackOperand(self._plain_weight(), self.config.pack_fmt if self.bit == 8 else self.config.pack_fmt4)
+                d.wpk = _backend.PackOperand(self._plain_weight(), _image_fmt(self.config, self.bit))
             d.joint = None
         state["_d"] = d
         return state
@@ -674,7 +679,7 @@ class MixLinear_GEMM(nn.Module):
                 return None
             wo = _wide(wo, _pad16(n))
         # (frozen: `ind` never changes again, so the quantise pass gets the kept bit mask of its columns instead of building one per launch)
-        extra = {} if self.act_dtype == torch.float16 else {"dtype": self.act_dtype}      # (mixq_linear_forward_bf16)
+        extra = _container_kw(self.act_dtype)                # (mixq_linear_forward_bf16)
         if self._decode_applies(M, wpk):
             extra["decode"] = True                           # (mixq_linear_forward_decode_bf16)
         return _backend.ForwardPlan(M, self.out_features, self.in_features, self.bit, self._sigma_f, inputs.stride(0), ind_buf, n, n_dev,
@@ -683,7 +688,7 @@ class MixLinear_GEMM(nn.Module):
     def _residual_rows(self, x, residual):
         """`residual` of forward() as the GEMM's [M, N] addend, or a RuntimeError that names the argument: no silent conversion."""
         want = tuple(x.shape[:-1]) + (self.out_features,)
-        dt = str(self.act_dtype).replace("torch.", "")
+        dt = _dtype_name(self.act_dtype)
         if not isinstance(residual, Tensor):
             raise RuntimeError(f"MixLinear_GEMM: residual must be a {dt} tensor of shape {want}, got {type(residual).__name__}")
         if residual.dtype != self.act_dtype:
@@ -725,7 +730,7 @@ class MixLinear_GEMM(nn.Module):
             # The argument block takes x by ADDRESS: what the two-call route checked in QuantFused is checked here on every call - a
             # kept block must not be replayed on a bf16 / fp32 tensor, another column count or a strided last dimension
             if inputs.dtype != self.act_dtype:
-                raise RuntimeError(f"MixLinear_GEMM: x must be {str(self.act_dtype).replace('torch.', '')}")
+                raise RuntimeError(f"MixLinear_GEMM: x must be {_dtype_name(self.act_dtype)}")
             if inputs.shape[1] != self.in_features:
                 raise RuntimeError(f"MixLinear_GEMM: x has {inputs.shape[1]} columns, the layer {self.in_features} input features")
             if inputs.stride(1) != 1 and M:
@@ -823,16 +828,10 @@ class MixLinear_GEMM(nn.Module):
         inputs = x.reshape(-1, x.shape[-1])
         M = inputs.shape[0]
         if inputs.dtype != self.act_dtype or (mul is not None and mul.dtype != self.act_dtype):
-            raise RuntimeError(f"MixLinear_GEMM: x and mul must be {str(self.act_dtype).replace('torch.', '')} (MixqConfig.act_dtype)")
+            raise RuntimeError(f"MixLinear_GEMM: x and mul must be {_dtype_name(self.act_dtype)} (MixqConfig.act_dtype)")
         if not self.forward_without_precondition_len == cache.ind.shape[0]:
             if cache.ind.shape[0]:
-                ind = cache.new_ind
-                weight_cache = _backend.DequantWeightCols(self.q_weight, self.scale_col, ind, self.bit)
-                if self._wstore is None:
-                    self._wstore = _ColStore(self.out_features, weight_cache.device,
-                                             self.weight_cache if (self.weight_cache is not None and self.ind.shape[0]) else None)
-                self._wstore.append(weight_cache)
-                self.weight_cache = self._wstore.view() if self._wstore.n else weight_cache
+                self._take_weight_cols(cache.new_ind)
                 self.ind = cache.ind
                 self.forward_without_precondition_len = self.ind.shape[0]
                 self._silu_calls = 0
@@ -845,7 +844,7 @@ class MixLinear_GEMM(nn.Module):
             wpk = self._packed_weight()
             if wpk is not None and \
                     _backend.amax_supported(M, self.out_features, self.in_features, _fmt_of(cache.q_xcache), _fmt_of(wpk),
-                                            **({} if self.act_dtype == torch.float16 else {"dtype": self.act_dtype})) and \
+                                            **_container_kw(self.act_dtype)) and \
                     getattr(amax_for, "act_dtype", torch.float16) == self.act_dtype:
                 target = amax_for.amax_target(M, x.device)
         extra = {} if target is None else {"row_amax": target[0], "col_mask": target[1]}

@@ -74,6 +74,24 @@ def _is_zero_addend(addend):
     return addend is None or getattr(addend, "_mixq_all_zero", False)
 
 
+def _pad16(n):
+    return (n + 15) // 16 * 16
+
+
+packed_rows = _pad16                     # rows of a packed operand image
+
+
+def _dtype_name(dtype):
+    """A dtype as messages print it: "float16", "bfloat16"."""
+    return str(dtype).replace("torch.", "")
+
+
+def _container_kw(dtype):
+    """How a caller says the container of a call's 16-bit tensors (FusedLinear, ForwardPlan, amax_supported): only where it is not float16 -
+    another backend behind the layers keeps the reference's argument lists."""
+    return {} if dtype == torch.float16 else {"dtype": dtype}
+
+
 def _check_ind(ind, what):
     if ind.dtype != torch.int32:
         raise RuntimeError(f"{what}: `ind` must be int32 (got {ind.dtype})")
@@ -233,7 +251,7 @@ def FindRowScale(x, x_scale, M, K, bit=8):
         raise RuntimeError("FindRowScale: shape mismatch")
     if bit not in (4, 8):
         raise RuntimeError("FindRowScale: bit must be 4 or 8")
-    KB, dt = (K, torch.int8) if bit == 8 else (K // 2, torch.uint8)
+    KB = _q_row_bytes(K, bit, FMT_PLAIN)
     global _pending_extract
     pend = _pending_extract
     if pend is not None:
@@ -244,17 +262,17 @@ def FindRowScale(x, x_scale, M, K, bit=8):
             _pending_extract = None
             pend.__dict__.pop("_mixq_pending", None)
             packed = _cfg.packed_operands and M > 0 and KB % 64 == 0
-            q = torch.empty((packed_rows(M) if packed else M, KB), dtype=dt, device=x.device)
+            q = _q_buffer(M, K, bit, FMT_P16X64 if packed else FMT_PLAIN, x.device)
             with torch._C.DisableTorchFunctionSubclass():
                 _capi.call("mixq_quant_fused", xp, ind_p.data_ptr(), ind_p.numel(), None, x_scale.data_ptr(), q.data_ptr(), pend.data_ptr(),
                            None, M, K, ldx, ldo_p, bit, 6.0, FMT_P16X64 if packed else FMT_PLAIN, _stream())
             return set_fmt(q[:M], FMT_P16X64) if packed else q
         _flush_pending_extract()
     if _cfg.packed_operands and M > 0 and KB % 64 == 0:
-        buf = torch.empty((packed_rows(M), KB), dtype=dt, device=x.device)
+        buf = _q_buffer(M, K, bit, FMT_P16X64, x.device)
         _capi.call("mixq_find_row_scale" + sfx, xp, x_scale.data_ptr(), buf.data_ptr(), M, K, ldx, bit, FMT_P16X64, _stream())
         return set_fmt(buf[:M], FMT_P16X64)              # same storage, same base pointer: an opaque handle of the reference's shape
-    q = torch.empty((M, KB), dtype=dt, device=x.device)
+    q = _q_buffer(M, K, bit, FMT_PLAIN, x.device)
     _capi.call("mixq_find_row_scale" + sfx, xp, x_scale.data_ptr(), q.data_ptr(), M, K, ldx, bit, FMT_PLAIN, _stream())
     return q
 
@@ -269,10 +287,6 @@ def FindRowScale(x, x_scale, M, K, bit=8):
 # the product to fp16 before it is added (torch.mm), the fused tail adds it in fp32 like the native operator (include/mixq_hip.h,
 # convention 2; <= 2 fp16 ulp apart).
 _wo_padded = {}        # (data_ptr, version, shape, stride) -> (weight_cache view, copy with a 16-column-padded pitch); pins its source
-
-
-def _pad16(n):
-    return (n + 15) // 16 * 16
 
 
 # ---- opt-in: extract + quantise as ONE pass behind the reference's two calls ----------------------------------------------
@@ -294,6 +308,55 @@ def _flush_pending_extract():
         t._run_extract()
 
 
+def _tensor_args(args, kwargs, cls):
+    """The `cls` instances among a torch function's arguments, one level of list / tuple included."""
+    for a in list(args) + list(kwargs.values()):
+        for b in (a if isinstance(a, (list, tuple)) else (a,)):
+            if isinstance(b, cls):
+                yield b
+
+
+class _Deferred(torch.Tensor):
+    """A result tensor whose values are computed (`_compute(*operands)`, into its own storage) only when something other than a mixlib GEMM
+    entry point looks at them: any torch function that is not a pure metadata query, or an export."""
+
+    @staticmethod
+    def _new(cls, shape, dtype, device, operands):
+        t = torch.Tensor._make_subclass(cls, torch.empty(shape, dtype=dtype, device=device))
+        t._mixq_args = operands
+        t._mixq_done = False
+        return t
+
+    def _materialize(self):
+        if getattr(self, "_mixq_done", True):
+            return
+        self._mixq_done = True
+        with torch._C.DisableTorchFunctionSubclass():
+            self._compute(*self._mixq_args)
+        self._mixq_args = None
+
+    # exports that do not go through __torch_function__ compute the values first
+    def __dlpack__(self, *args, **kwargs):
+        self._materialize()
+        with torch._C.DisableTorchFunctionSubclass():
+            return self.as_subclass(torch.Tensor).__dlpack__(*args, **kwargs)
+
+    @property
+    def __cuda_array_interface__(self):
+        self._materialize()
+        with torch._C.DisableTorchFunctionSubclass():
+            return self.as_subclass(torch.Tensor).__cuda_array_interface__
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        if func not in _meta_funcs():
+            for t in _tensor_args(args, kwargs, _Deferred):
+                t._materialize()
+        with torch._C.DisableTorchFunctionSubclass():
+            return func(*args, **kwargs)
+
+
 class OutlierActivations(torch.Tensor):
     """x_out [M,n] as returned by ExtractOutliersAndSetToZeros under configure(fused_outliers=True): a view of 16-column-padded storage
     (what the GEMM's tail reads) that recognises the reference's torch.mm with weight_cache.T."""
@@ -312,11 +375,10 @@ class OutlierActivations(torch.Tensor):
         kwargs = kwargs or {}
         T = torch.Tensor
         if func not in _meta_funcs():
-            for a in list(args) + list(kwargs.values()):
-                for b in (a if isinstance(a, (list, tuple)) else (a,)):
-                    if isinstance(b, OutlierActivations) and "_mixq_pending" in b.__dict__:
-                        _flush_pending_extract()
-                        b._run_extract()
+            for b in _tensor_args(args, kwargs, OutlierActivations):
+                if "_mixq_pending" in b.__dict__:
+                    _flush_pending_extract()
+                    b._run_extract()
         if _cfg.fused_outliers and not kwargs and len(args) == 2 and func in (torch.mm, torch.matmul, T.mm, T.matmul, T.__matmul__):
             a, b = args
             if (isinstance(a, OutlierActivations) and isinstance(b, torch.Tensor) and not isinstance(b, OutlierActivations)
@@ -327,36 +389,15 @@ class OutlierActivations(torch.Tensor):
             return func(*args, **kwargs)
 
 
-class PendingOutlierProduct(torch.Tensor):
+class PendingOutlierProduct(_Deferred):
     """torch.mm(activation_outliers, weight_cache.T), deferred: see ShimConfig.fused_outliers."""
 
     @staticmethod
     def __new__(cls, xo, wo_t):
-        t = torch.Tensor._make_subclass(cls, torch.empty((xo.shape[0], wo_t.shape[1]), dtype=torch.float16, device=xo.device))
-        t._mixq_args = (xo, wo_t)
-        t._mixq_done = False
-        return t
+        return _Deferred._new(cls, (xo.shape[0], wo_t.shape[1]), torch.float16, xo.device, (xo, wo_t))
 
-    def _materialize(self):
-        if getattr(self, "_mixq_done", True):
-            return
-        self._mixq_done = True
-        with torch._C.DisableTorchFunctionSubclass():
-            xo, wo_t = self._mixq_args
-            torch.mm(xo.as_subclass(torch.Tensor), wo_t, out=self.as_subclass(torch.Tensor))
-        self._mixq_args = None
-
-    # exports that do not go through __torch_function__ compute the values first
-    def __dlpack__(self, *args, **kwargs):
-        self._materialize()
-        with torch._C.DisableTorchFunctionSubclass():
-            return self.as_subclass(torch.Tensor).__dlpack__(*args, **kwargs)
-
-    @property
-    def __cuda_array_interface__(self):
-        self._materialize()
-        with torch._C.DisableTorchFunctionSubclass():
-            return self.as_subclass(torch.Tensor).__cuda_array_interface__
+    def _compute(self, xo, wo_t):
+        torch.mm(xo.as_subclass(torch.Tensor), wo_t, out=self.as_subclass(torch.Tensor))
 
     def _operands(self):
         """(x_out, ldxo-ready tensor, w_out padded, n) for the fused tail, or None once materialised."""
@@ -387,20 +428,6 @@ class PendingOutlierProduct(torch.Tensor):
                 wo = wp[:, :n]
         return xo, wo, n
 
-    @classmethod
-    def __torch_function__(cls, func, types, args=(), kwargs=None):
-        kwargs = kwargs or {}
-        if func not in _meta_funcs():
-            for a in list(args) + list(kwargs.values()):
-                if isinstance(a, PendingOutlierProduct):
-                    a._materialize()
-                elif isinstance(a, (list, tuple)):
-                    for b in a:
-                        if isinstance(b, PendingOutlierProduct):
-                            b._materialize()
-        with torch._C.DisableTorchFunctionSubclass():
-            return func(*args, **kwargs)
-
 
 def ExtractOutliersAndSetToZeros(ind, x):
     """mixlib.ExtractOutliersAndSetToZeros(ind, x) -> x_out [M,n]; zeroes columns `ind` of x IN PLACE (linear.py:189,205).  A bfloat16 x
@@ -416,7 +443,7 @@ def ExtractOutliersAndSetToZeros(ind, x):
     n = ind.numel()
     _flush_pending_extract()                                 # (an earlier deferred extraction runs first: program order)
     if _cfg.fused_outliers and n:
-        buf = torch.empty((M, _pad16(n)), dtype=torch.float16, device=x.device)          # (columns >= n: never read as values)
+        buf = _outlier_buffer(M, n, torch.float16, x.device)
         out = buf[:, :n].as_subclass(OutlierActivations)
         if _cfg.fused_prepass and x.dim() == 2:
             out._mixq_pending = (ind, x, buf.shape[1])
@@ -440,6 +467,29 @@ def _outlier_operands(addend):
     return None
 
 
+def _addend_operand(addend, dtype=None, drop_zero=True):
+    """(ptr, lda) of a GEMM's addend / multiplier.  The cache's zero tag (or None) is no addend unless the slot carries a multiplier; a
+    deferred outlier product is computed first.  `dtype` (FusedLinear: the call's container): the addend must have it, and a base that is
+    not 8-byte aligned goes through a copy."""
+    if drop_zero and _is_zero_addend(addend):
+        return None, 0
+    if isinstance(addend, PendingOutlierProduct):
+        addend._materialize()
+    _dev_check(addend)
+    if dtype is not None:
+        _check_same_dtype(dtype, "FusedLinear", addend=addend)
+        addend = _aligned_addend(addend)
+    return _rows(addend, "addend")
+
+
+def _fused_args(q_x, q_w, x_scale, scale_col, outliers, n_dev, addend, bias, y, M, N, K, act, layout, pair=False):
+    """The argument list of a fused GEMM entry point in front of its trailing arguments and the stream (include/mixq_hip.h).  outliers:
+    (x_out, ldxo, w_out, ldwo, n); addend: (ptr, lda).  pair: the `_pair_bf16` entry points' list, which has no addend and no act."""
+    head = (q_x.data_ptr(), q_w.data_ptr(), x_scale.data_ptr(), scale_col.data_ptr(), *outliers, _ptr(n_dev))
+    tail = (_ptr(bias), y.data_ptr(), y.stride(0), M, N, K)
+    return head + tail + (layout,) if pair else head + addend + tail + (act, layout)
+
+
 def _fused_dequant(q_x, q_w, x_scale, scale_col, addend, M, N, K, bit, act):
     _dev_check(q_x, q_w, x_scale, scale_col)
     if fmt_of(q_x) != FMT_PLAIN:
@@ -447,22 +497,13 @@ def _fused_dequant(q_x, q_w, x_scale, scale_col, addend, M, N, K, bit, act):
         if fmt_of(q_w) == FMT_PLAIN:
             raise RuntimeError("mixq_amd.mixlib: packed q_x with a plain weight that cannot be packed (K % 64)")
     y = torch.empty((M, N), dtype=torch.float16, device=q_x.device)
-    xop, ldxo, wop, ldwo, n_out = None, 0, None, 0, 0
     outl = _outlier_operands(addend)
     if outl is not None and tuple(addend.shape) == (M, N):
-        xop, ldxo, wop, ldwo, n_out, _keep = outl            # the product runs as the GEMM's fp16 tail; nothing is added afterwards
-        ap, lda = None, 0
-    elif _is_zero_addend(addend):
-        ap, lda = None, 0
+        outl, _keep, ap = outl[:5], outl[5], (None, 0)       # the product runs as the GEMM's fp16 tail; nothing is added afterwards
     else:
-        if isinstance(addend, PendingOutlierProduct):
-            addend._materialize()
-        _dev_check(addend)
-        ap, lda = _rows(addend, "addend")
-    fn = "mixq_gemm_i8_fused" if bit == 8 else "mixq_gemm_i4_fused"
-    _capi.call(fn, q_x.data_ptr(), q_w.data_ptr(), x_scale.data_ptr(), scale_col.data_ptr(),
-               xop, ldxo, wop, ldwo, n_out, None, ap, lda, None, y.data_ptr(), N, M, N, K, act, _layout_bits(fmt_of(q_x), fmt_of(q_w)),
-               _stream())
+        outl, ap = (None, 0, None, 0, 0), _addend_operand(addend)
+    _capi.call("mixq_gemm_i8_fused" if bit == 8 else "mixq_gemm_i4_fused",
+               *_fused_args(q_x, q_w, x_scale, scale_col, outl, None, ap, None, y, M, N, K, act, _layout_bits(fmt_of(q_x), fmt_of(q_w))), _stream())
     return y
 
 
@@ -503,7 +544,7 @@ def _meta_funcs():
     return _META_FUNCS
 
 
-class PendingGemmI32(torch.Tensor):
+class PendingGemmI32(_Deferred):
     """The int32 [M,N] tensor `mixlib.gemm` returns, with the product itself deferred.
 
     On gfx950 torch reports capability major 9, so the UNCHANGED reference takes its `arch == 9` branch
@@ -516,47 +557,12 @@ class PendingGemmI32(torch.Tensor):
 
     @staticmethod
     def __new__(cls, q_x, q_w, M, N, K):
-        t = torch.Tensor._make_subclass(cls, torch.empty((M, N), dtype=torch.int32, device=q_x.device))
-        t._mixq_args = (q_x, q_w, M, N, K)
-        t._mixq_done = False
-        return t
+        return _Deferred._new(cls, (M, N), torch.int32, q_x.device, (q_x, q_w, M, N, K))
 
-    def _materialize(self):
-        if getattr(self, "_mixq_done", True):
-            return
-        self._mixq_done = True
-        with torch._C.DisableTorchFunctionSubclass():
-            q_x, q_w, M, N, K = self._mixq_args
-            if fmt_of(q_x) != FMT_PLAIN:                     # ShimConfig.packed_operands: the raw kernel wants the plain matrix back
-                q_x = UnpackOperand(q_x.as_strided((packed_rows(M), K), (K, 1), q_x.storage_offset()), M, fmt_of(q_x))
-            _capi.call("mixq_gemm_i8", q_x.data_ptr(), q_w.data_ptr(), self.data_ptr(), N, M, N, K, _stream())
-        self._mixq_args = None
-
-    # exports that do not go through __torch_function__ compute the values first
-    def __dlpack__(self, *args, **kwargs):
-        self._materialize()
-        with torch._C.DisableTorchFunctionSubclass():
-            return self.as_subclass(torch.Tensor).__dlpack__(*args, **kwargs)
-
-    @property
-    def __cuda_array_interface__(self):
-        self._materialize()
-        with torch._C.DisableTorchFunctionSubclass():
-            return self.as_subclass(torch.Tensor).__cuda_array_interface__
-
-    @classmethod
-    def __torch_function__(cls, func, types, args=(), kwargs=None):
-        kwargs = kwargs or {}
-        if func not in _meta_funcs():
-            for a in list(args) + list(kwargs.values()):
-                if isinstance(a, PendingGemmI32):
-                    a._materialize()
-                elif isinstance(a, (list, tuple)):
-                    for b in a:
-                        if isinstance(b, PendingGemmI32):
-                            b._materialize()
-        with torch._C.DisableTorchFunctionSubclass():
-            return func(*args, **kwargs)
+    def _compute(self, q_x, q_w, M, N, K):
+        if fmt_of(q_x) != FMT_PLAIN:                         # ShimConfig.packed_operands: the raw kernel wants the plain matrix back
+            q_x = UnpackOperand(q_x.as_strided((packed_rows(M), K), (K, 1), q_x.storage_offset()), M, fmt_of(q_x))
+        _capi.call("mixq_gemm_i8", q_x.data_ptr(), q_w.data_ptr(), self.data_ptr(), N, M, N, K, _stream())
 
 
 def _lazy():
@@ -589,12 +595,7 @@ def _dequant(y32, x_scale, scale_col, addend, bit, M, N, act):
         q_x, q_w, _, _, K = y32._mixq_args                  # the product was never needed on its own: one fused kernel
         return _fused_dequant(q_x, q_w, x_scale, scale_col, addend, M, N, K, 8, act)
     y = torch.empty((M, N), dtype=torch.float16, device=y32.device)
-    if _is_zero_addend(addend):
-        ap, lda = None, 0
-    else:
-        if isinstance(addend, PendingOutlierProduct):
-            addend._materialize()                            # the literal pair adds the product as the reference computed it
-        ap, lda = _rows(addend, "addend")
+    ap, lda = _addend_operand(addend)                        # (a deferred product: the literal pair adds it as the reference computed it)
     yp, ldy32 = _rows(y32, "y32")
     _capi.call("mixq_dequant", yp, ldy32, x_scale.data_ptr(), scale_col.data_ptr(), ap, lda, None, y.data_ptr(), N, M, N,
                act, _stream())
@@ -628,10 +629,6 @@ def unpack_int4_to_fp16(q_w, ind):
 # ------------------------------------------------------------------------------------------------------------
 # MI355X additions (fused forms)
 # ------------------------------------------------------------------------------------------------------------
-def packed_rows(rows):
-    return (rows + 15) // 16 * 16
-
-
 def PackOperand(q, fmt=FMT_P16X64):
     """Re-tile a plain [R,KB] int8/uint8 operand into a packed layout (include/mixq_hip.h).  Returns a [roundup(R,16), KB]
     tensor of the same dtype holding the packed bytes (NOT addressable as a matrix), tagged with its format."""
@@ -676,6 +673,21 @@ def _q_row_bytes(K, bit, fmt):
     return K if bit == 8 else K // 2
 
 
+def _q_spec(M, K, bit, fmt):
+    """(shape, dtype) of the quantised-activation buffer of M rows: the rows of a packed image are padded to 16."""
+    return (packed_rows(M) if fmt else M, _q_row_bytes(K, bit, fmt)), (torch.int8 if bit == 8 else torch.uint8)
+
+
+def _q_buffer(M, K, bit, fmt, device):
+    shape, dtype = _q_spec(M, K, bit, fmt)
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
+def _outlier_buffer(M, n, dtype, device):
+    """x_out for n outlier columns: the row stride padded to 16 elements (columns >= n: never read as values)."""
+    return torch.empty((M, _pad16(n)), dtype=dtype, device=device)
+
+
 def _want_fmt(packed, fmt):
     if fmt is not None:
         return fmt
@@ -695,6 +707,32 @@ def _check_kept_map(col_mask, K, who):
                            f"(bit words, count word, pad, K 16-bit AND-masks; linear.kept_outlier_map), got {col_mask.numel()} x {col_mask.element_size()} bytes")
 
 
+def _quant_pass(who, name, sfx, x, xrows, norm, ind, x_scale, bit, sigma, x_out, flag, n_dev, fmt, col_mask):
+    """The body QuantFused and RMSNormQuantFused share: allocate q_x (and x_out), launch `name` (its `_masked` form under a kept outlier map)
+    with the container's suffix.  x: [M,K] behind xrows = (ptr, ldx).  norm: None, or the norm form's (weight ptr, out ptr, out's row stride, eps)."""
+    M, K = x.shape
+    n = 0 if ind is None else ind.numel()
+    q = _q_buffer(M, K, bit, fmt, x.device)
+    if n:
+        ind = _check_ind(ind, who)
+        if x_out is None:
+            x_out = _outlier_buffer(M, n, x.dtype, x.device)
+        elif x_out.dtype != x.dtype:
+            raise RuntimeError(f"{who}: x_out must be {x.dtype} like x, got {x_out.dtype}")
+        op, ldo = _rows(x_out, "x_out")
+        ip = ind.data_ptr()
+    else:
+        op, ldo, ip = None, 0, None
+    mask = ()
+    if col_mask is not None and n:
+        _check_kept_map(col_mask, K, who)
+        name, mask = name + "_masked", (col_mask.data_ptr(), col_mask.numel())
+    front, lds = ((), (xrows[1], ldo)) if norm is None else (norm[:2], (xrows[1], norm[2], ldo, float(norm[3])))
+    _capi.call(name + sfx, xrows[0], *front, ip, n, _ptr(n_dev), *mask, x_scale.data_ptr(), q.data_ptr(), op, _ptr(flag), M, K, *lds,
+               bit, float(sigma), fmt, _stream())
+    return set_fmt(q, fmt), (x_out[:, :n] if n else None)
+
+
 def QuantFused(x, ind, x_scale, bit, sigma, x_out=None, flag=None, n_dev=None, packed=False, fmt=None, col_mask=None):
     """(i)+(ii) in one pass over X: extract/zero the known outlier columns `ind`, per-row scale into x_scale[0:M],
     quantise, and raise the device-side misprediction flag.  Returns (q_x, x_out_view[M,n]).  With fmt = FMT_P16X64 /
@@ -705,33 +743,11 @@ def QuantFused(x, ind, x_scale, bit, sigma, x_out=None, flag=None, n_dev=None, p
     A bfloat16 x runs the `_bf16` twins: x_out is then bfloat16, x_scale stays float16."""
     _dev_check(x, x_scale, ind, col_mask)
     fmt = _want_fmt(packed, fmt)
-    xp, ldx = _rows(x, "x")
-    M, K = x.shape
+    xrows = _rows(x, "x")
     sfx = _act_suffix(x, "QuantFused")
-    if x_scale.numel() < M:
-        raise RuntimeError(f"QuantFused: x_scale holds {x_scale.numel()} rows, the batch has {M} (MixLibCache.inputdim too small)")
-    n = 0 if ind is None else ind.numel()
-    q = torch.empty((packed_rows(M) if fmt else M, _q_row_bytes(K, bit, fmt)),
-                    dtype=torch.int8 if bit == 8 else torch.uint8, device=x.device)
-    if n:
-        ind = _check_ind(ind, "QuantFused")
-        if x_out is None:
-            ldo = (n + 15) // 16 * 16
-            x_out = torch.empty((M, ldo), dtype=x.dtype, device=x.device)
-        elif x_out.dtype != x.dtype:
-            raise RuntimeError(f"QuantFused: x_out must be {x.dtype} like x, got {x_out.dtype}")
-        op, ldo = _rows(x_out, "x_out")
-        ip = ind.data_ptr()
-    else:
-        op, ldo, ip = None, 0, None
-    if col_mask is not None and n:
-        _check_kept_map(col_mask, K, "QuantFused")
-        _capi.call("mixq_quant_fused_masked" + sfx, xp, ip, n, _ptr(n_dev), col_mask.data_ptr(), col_mask.numel(), x_scale.data_ptr(), q.data_ptr(), op, _ptr(flag), M, K,
-                   ldx, ldo, bit, float(sigma), fmt, _stream())
-    else:
-        _capi.call("mixq_quant_fused" + sfx, xp, ip, n, _ptr(n_dev), x_scale.data_ptr(), q.data_ptr(), op, _ptr(flag), M, K, ldx,
-                   ldo, bit, float(sigma), fmt, _stream())
-    return set_fmt(q, fmt), (x_out[:, :n] if n else None)
+    if x_scale.numel() < x.shape[0]:
+        raise RuntimeError(f"QuantFused: x_scale holds {x_scale.numel()} rows, the batch has {x.shape[0]} (MixLibCache.inputdim too small)")
+    return _quant_pass("QuantFused", "mixq_quant_fused", sfx, x, xrows, None, ind, x_scale, bit, sigma, x_out, flag, n_dev, fmt, col_mask)
 
 
 def FindRowScalePacked(x, x_scale, M, K, bit=8, fmt=FMT_P16X64):
@@ -741,7 +757,7 @@ def FindRowScalePacked(x, x_scale, M, K, bit=8, fmt=FMT_P16X64):
     xp, ldx = _rows(x, "x")
     if x_scale.numel() < M:
         raise RuntimeError(f"FindRowScalePacked: x_scale holds {x_scale.numel()} rows, the batch has {M}")
-    q = torch.empty((packed_rows(M), _q_row_bytes(K, bit, fmt)), dtype=torch.int8 if bit == 8 else torch.uint8, device=x.device)
+    q = _q_buffer(packed_rows(M), K, bit, fmt, x.device)
     _capi.call("mixq_find_row_scale" + sfx, xp, x_scale.data_ptr(), q.data_ptr(), M, K, ldx, bit, fmt, _stream())
     return set_fmt(q, fmt)
 
@@ -793,23 +809,13 @@ PAIR_LAUNCH_BF16 = True                  # ... and with dtype=torch.bfloat16 (AB
 
 
 def _pair_bf16_entry(name):
-    """An ABI 1.5 entry point of the loaded library.  mixq_version() does not tell 1.5 from 1.3 (the number is pinned), so the symbol itself is
-    probed: a library built before it says so here, by name - nothing falls back to another route."""
-    fn = getattr(_capi.load(), name, None)
-    if fn is None:
-        raise RuntimeError(f"FusedLinear: the loaded library ({_capi.LIB_PATH}) does not export {name} (ABI 1.5, the joint gate / up launch in "
-                           f"bfloat16); rebuild it")
-    return fn
+    """An ABI 1.5 entry point of the loaded library (_capi.entry: a library built before it says so, by name)."""
+    return _capi.entry(name, "FusedLinear")
 
 
 def _decode_bf16_entry(name, who="FusedLinear"):
-    """An ABI 1.7 entry point of the loaded library (the small-batch kernel in bfloat16), probed by symbol like the ABI 1.5 ones: a library
-    built before it says so here, by name - nothing falls back to the other route."""
-    fn = getattr(_capi.load(), name, None)
-    if fn is None:
-        raise RuntimeError(f"{who}: the loaded library ({_capi.LIB_PATH}) does not export {name} (ABI 1.7, the small-batch form in "
-                           f"bfloat16); rebuild it")
-    return fn
+    """An ABI 1.7 entry point of the loaded library (the small-batch kernel in bfloat16), probed like the ABI 1.5 ones."""
+    return _capi.entry(name, who)
 
 
 def decode_pick(M, N, K, bit, x_fmt, w_fmt):
@@ -817,7 +823,7 @@ def decode_pick(M, N, K, bit, x_fmt, w_fmt):
     the fp16 entry points' automatic plan takes it) and FusedLinear(..., decode=True) / ForwardPlan(..., decode=True) serve it."""
     if x_fmt != FMT_P16X64 or w_fmt not in (FMT_P16X64, FMT_F16X64):
         return False
-    rc = _decode_bf16_entry("mixq_gemm_decode_pick_bf16", "decode_pick")(M, N, K, bit, _layout_bits(x_fmt, w_fmt))
+    rc = _capi.entry("mixq_gemm_decode_pick_bf16", "decode_pick")(M, N, K, bit, _layout_bits(x_fmt, w_fmt))
     if rc < 0:
         raise _capi.MixqError("mixq_gemm_decode_pick_bf16", rc)
     return rc == 1
@@ -830,13 +836,40 @@ def _check_same_dtype(dtype, who, **tensors):
             raise RuntimeError(f"{who}: {name} must be {dtype} like the call's other 16-bit tensors (dtype={dtype}), got {t.dtype}")
 
 
+def _refuse_decode(who, auto, dtype, act, row_amax=None):
+    """What `decode=True` does not serve, said in front of everything else."""
+    why = (f"dtype=float16 takes the small-batch kernel by itself (the automatic route of {auto})" if dtype != torch.bfloat16
+           else "the small-batch kernel has no row-maximum side output" if row_amax is not None
+           else "the small-batch kernel has no paired gate / up form (ACT_SILU_PAIR)" if act == ACT_SILU_PAIR else None)
+    if why:
+        raise RuntimeError(f"{who}: decode=True: {why}")
+
+
+def _fused_route(bit, sfx, act, row_amax, col_mask, decode):
+    """Which entry point a FusedLinear call takes: (name, is it the paired list, the arguments between the list and the stream)."""
+    b = 8 if bit == 8 else 4
+    if sfx and act == ACT_SILU_PAIR:                         # (entry points of their own: no addend, no act argument)
+        return f"mixq_gemm_i{b}_pair_bf16", True, ((_ptr(row_amax), _ptr(col_mask)) if bit == 8 else ())
+    if row_amax is not None:
+        return "mixq_gemm_i8_fused_amax" + sfx, False, (row_amax.data_ptr(), _ptr(col_mask))
+    return (f"mixq_gemm_i{b}_decode_bf16" if decode else f"mixq_gemm_i{b}_fused" + sfx), False, ()
+
+
+def _plan_route(dtype, act, decode):
+    """Which entry point a ForwardPlan runs: mixq_linear_forward, its `_bf16` twin, or (decode) mixq_linear_forward_decode_bf16."""
+    name = "mixq_linear_forward" + _act_suffix(dtype, "ForwardPlan")
+    if decode:
+        _refuse_decode("ForwardPlan", "mixq_linear_forward", dtype, act)
+        name = "mixq_linear_forward_decode_bf16"
+    return name
+
+
 def amax_supported(M, N, K, x_fmt, w_fmt, dtype=torch.float16):
     """True when the GEMM can leave the next layer's row maxima as a side output for this problem (mixq_gemm_amax_supported; `dtype`: the
     container of y - the bf16 forms serve every batch size)."""
     if x_fmt != FMT_P16X64 or w_fmt != FMT_F16X64:
         return False
-    fn = getattr(_capi.load(), "mixq_gemm_amax_supported" + _act_suffix(dtype, "amax_supported"))
-    return bool(fn(M, N, K, X_PACKED | W_F16X64))
+    return bool(_capi.entry("mixq_gemm_amax_supported" + _act_suffix(dtype, "amax_supported"))(M, N, K, X_PACKED | W_F16X64))
 
 
 def FusedLinear(q_x, q_w, x_scale, scale_col, x_out, w_out, n_out, bias, M, N, K, bit=8, act=ACT_NONE, n_out_dev=None,
@@ -855,13 +888,8 @@ def FusedLinear(q_x, q_w, x_scale, scale_col, x_out, w_out, n_out, bias, M, N, K
     `decode` (bfloat16 only, M <= 32): the small-batch kernel, mixq_gemm_i8_decode_bf16 / mixq_gemm_i4_decode_bf16 (ABI 1.7; ask decode_pick
     where it is the route of choice).  It has no row-maximum side output and no paired form, and fp16 takes the kernel by itself."""
     if decode:
-        why = ("dtype=float16 takes the small-batch kernel by itself (the automatic route of mixq_gemm_i8_fused)" if dtype != torch.bfloat16
-               else "the small-batch kernel has no row-maximum side output" if row_amax is not None
-               else "the small-batch kernel has no paired gate / up form (ACT_SILU_PAIR)" if act == ACT_SILU_PAIR else None)
-        if why:
-            raise RuntimeError(f"FusedLinear: decode=True: {why}")
-        fn_decode_name = "mixq_gemm_i8_decode_bf16" if bit == 8 else "mixq_gemm_i4_decode_bf16"
-        fn_decode = _decode_bf16_entry(fn_decode_name)
+        _refuse_decode("FusedLinear", "mixq_gemm_i8_fused", dtype, act, row_amax)
+        _decode_bf16_entry("mixq_gemm_i8_decode_bf16" if bit == 8 else "mixq_gemm_i4_decode_bf16")
     _dev_check(q_x, q_w, x_scale, scale_col, row_amax, col_mask)
     if x_scale.numel() < M or scale_col.numel() < N:
         raise RuntimeError("FusedLinear: x_scale / scale_col are shorter than M / N")
@@ -870,60 +898,25 @@ def FusedLinear(q_x, q_w, x_scale, scale_col, x_out, w_out, n_out, bias, M, N, K
     # (ACT_SILU_PAIR: N counts the interleaved gate / up rows, the product has N / 2 columns)
     if act == ACT_SILU_PAIR and (N % 16 or not _is_zero_addend(addend)):
         raise RuntimeError("FusedLinear: ACT_SILU_PAIR needs N % 16 == 0 and takes no addend")
-    sfx = _act_suffix(dtype, "FusedLinear")
-    pair_bf16 = bool(sfx) and act == ACT_SILU_PAIR           # (entry points of their own: no addend, no act argument)
-    if pair_bf16:
-        fn_pair = _pair_bf16_entry("mixq_gemm_i8_pair_bf16" if bit == 8 else "mixq_gemm_i4_pair_bf16")
+    name, pair, trailing = _fused_route(bit, _act_suffix(dtype, "FusedLinear"), act, row_amax, col_mask, decode)
+    if pair:
+        _pair_bf16_entry(name)
     y = out if out is not None else torch.empty((M, N // 2 if act == ACT_SILU_PAIR else N), dtype=dtype, device=q_x.device)
     _check_same_dtype(dtype, "FusedLinear", out=out)
     if out is not None:
         _check_out(out, M, N // 2 if act == ACT_SILU_PAIR else N, q_x.device, "FusedLinear")
+    outl = (None, 0, None, 0, 0)
     if n_out and x_out is not None and w_out is not None:
         _check_same_dtype(dtype, "FusedLinear", x_out=x_out, w_out=w_out)
-        xop, ldxo = _rows(x_out, "x_out")
-        wop, ldwo = _rows(w_out, "w_out")
-    else:
-        xop = wop = None
-        ldxo = ldwo = 0
-        n_out = 0
-    if act == ACT_SILU_MUL:                  # the addend slot carries the multiplier (silu(gate) * up): never dropped
-        if addend is None:
-            raise RuntimeError("FusedLinear: ACT_SILU_MUL needs the multiplier in `addend`")
-        _dev_check(addend)
-        _check_same_dtype(dtype, "FusedLinear", addend=addend)
-        ap, lda = _rows(_aligned_addend(addend), "addend")
-    elif _is_zero_addend(addend):
-        ap, lda = None, 0
-    else:
-        if isinstance(addend, PendingOutlierProduct):
-            addend._materialize()
-        _dev_check(addend)
-        _check_same_dtype(dtype, "FusedLinear", addend=addend)
-        ap, lda = _rows(_aligned_addend(addend), "addend")
+        outl = _rows(x_out, "x_out") + _rows(w_out, "w_out") + (n_out,)
+    if act == ACT_SILU_MUL and addend is None:               # the addend slot carries the multiplier (silu(gate) * up): never dropped
+        raise RuntimeError("FusedLinear: ACT_SILU_MUL needs the multiplier in `addend`")
+    ap = _addend_operand(addend, dtype, drop_zero=act != ACT_SILU_MUL)
     if row_amax is not None:
         if bit != 8 or row_amax.numel() < M or row_amax.element_size() != 4:
             raise RuntimeError("FusedLinear: row_amax needs an int8 GEMM and a 4-byte buffer of at least M entries")
-    if pair_bf16:
-        args = (q_x.data_ptr(), q_w.data_ptr(), x_scale.data_ptr(), scale_col.data_ptr(), xop, ldxo, wop, ldwo, n_out, _ptr(n_out_dev),
-                _ptr(bias), y.data_ptr(), y.stride(0), M, N, K, _layout_bits(x_fmt, w_fmt))
-        rc = fn_pair(*args, _ptr(row_amax), _ptr(col_mask), _stream()) if bit == 8 else fn_pair(*args, _stream())
-        if rc != 0:
-            raise _capi.MixqError("mixq_gemm_i8_pair_bf16" if bit == 8 else "mixq_gemm_i4_pair_bf16", rc)
-        return y
-    if row_amax is not None:
-        _capi.call("mixq_gemm_i8_fused_amax" + sfx, q_x.data_ptr(), q_w.data_ptr(), x_scale.data_ptr(), scale_col.data_ptr(), xop, ldxo, wop, ldwo,
-                   n_out, _ptr(n_out_dev), ap, lda, _ptr(bias), y.data_ptr(), y.stride(0), M, N, K, act, _layout_bits(x_fmt, w_fmt),
-                   row_amax.data_ptr(), _ptr(col_mask), _stream())
-        return y
-    if decode:
-        rc = fn_decode(q_x.data_ptr(), q_w.data_ptr(), x_scale.data_ptr(), scale_col.data_ptr(), xop, ldxo, wop, ldwo, n_out,
-                       _ptr(n_out_dev), ap, lda, _ptr(bias), y.data_ptr(), y.stride(0), M, N, K, act, _layout_bits(x_fmt, w_fmt), _stream())
-        if rc != 0:
-            raise _capi.MixqError(fn_decode_name, rc)
-        return y
-    fn = ("mixq_gemm_i8_fused" if bit == 8 else "mixq_gemm_i4_fused") + sfx
-    _capi.call(fn, q_x.data_ptr(), q_w.data_ptr(), x_scale.data_ptr(), scale_col.data_ptr(), xop, ldxo, wop, ldwo, n_out,
-               _ptr(n_out_dev), ap, lda, _ptr(bias), y.data_ptr(), y.stride(0), M, N, K, act, _layout_bits(x_fmt, w_fmt), _stream())
+    _capi.call(name, *_fused_args(q_x, q_w, x_scale, scale_col, outl, n_out_dev, ap, bias, y, M, N, K, act, _layout_bits(x_fmt, w_fmt), pair), *trailing,
+               _stream())
     return y
 
 
@@ -937,16 +930,9 @@ class ForwardPlan:
     def __init__(self, M, N, K, bit, sigma, ldx, ind_buf, n, n_dev, x_scale, q_w, scale_col, w_out, bias, qfmt, act=ACT_NONE, kept_mask=None, dtype=torch.float16, decode=False):
         import ctypes as C
         # dtype: the container of x, x_out, w_out and y (float16, or bfloat16: mixq_linear_forward_bf16); checked against x on every run
-        self.dtype, self.fn_name = dtype, "mixq_linear_forward" + _act_suffix(dtype, "ForwardPlan")
         # decode (bfloat16, M <= 32): the small-batch GEMM behind the same block, mixq_linear_forward_decode_bf16 (ABI 1.7)
-        self.decode = bool(decode)
-        if decode:
-            why = ("dtype=float16 takes the small-batch kernel by itself (the automatic route of mixq_linear_forward)" if dtype != torch.bfloat16
-                   else "the small-batch kernel has no paired gate / up form (ACT_SILU_PAIR)" if act == ACT_SILU_PAIR else None)
-            if why:
-                raise RuntimeError(f"ForwardPlan: decode=True: {why}")
-            self.fn_name = "mixq_linear_forward_decode_bf16"
-            _decode_bf16_entry(self.fn_name, "ForwardPlan")
+        self.dtype, self.decode, self.fn_name = dtype, bool(decode), _plan_route(dtype, act, decode)
+        fn = _capi.entry(self.fn_name, "ForwardPlan")
         _dev_check(x_scale, q_w, scale_col, ind_buf, n_dev, w_out, bias)
         if x_scale.numel() < M or scale_col.numel() < N:
             raise RuntimeError("ForwardPlan: x_scale / scale_col are shorter than M / N")
@@ -966,7 +952,7 @@ class ForwardPlan:
                 raise RuntimeError("ForwardPlan: w_out row stride must be >= the outlier capacity and a multiple of 8")
             a.w_out, a.ldwo = wop, ldwo
         a.ldy = N
-        self.args, self.ref, self.fn = a, C.byref(a), getattr(_capi.load(), self.fn_name)
+        self.args, self.ref, self.fn = a, C.byref(a), fn
         # kept_mask: the layer's kept outlier map of `ind` (include/mixq_hip.h: bits, count, AND-masks): the quantise pass then needs one memory round trip
         if kept_mask is not None:
             _dev_check(kept_mask)
@@ -977,7 +963,7 @@ class ForwardPlan:
         import threading
         self.lock = threading.Lock()                   # (the argument block is ONE structure: filled and handed over under the lock, see run)
         self.captured = False                          # ran under hipGraph capture: a graph out there replays the addresses this plan carries
-        self.q_shape, self.q_dtype = (packed_rows(M) if qfmt else M, _q_row_bytes(K, bit, qfmt)), (torch.int8 if bit == 8 else torch.uint8)
+        self.q_shape, self.q_dtype = _q_spec(M, K, bit, qfmt)
 
     def run(self, x, row_amax=None, col_mask=None, addend=None):
         """x: [M,K] in the plan's dtype with the row stride the plan was built for.  Returns (y [M,N], q_x, x_out [M,n] or None).
@@ -993,7 +979,7 @@ class ForwardPlan:
             if not isinstance(addend, torch.Tensor) or addend.device != dev:
                 raise RuntimeError(f"ForwardPlan: addend lives on {getattr(addend, 'device', type(addend).__name__)}, the plan was built for {dev}")
             if addend.dtype != self.dtype or addend.dim() != 2 or tuple(addend.shape) != (self.M, self.N) or addend.stride(1) != 1 or (self.M > 1 and addend.stride(0) % 4):
-                raise RuntimeError(f"ForwardPlan: addend must be {str(self.dtype).replace('torch.', '')} [{self.M}, {self.N}] with a contiguous last dimension and a row "
+                raise RuntimeError(f"ForwardPlan: addend must be {_dtype_name(self.dtype)} [{self.M}, {self.N}] with a contiguous last dimension and a row "
                                    f"stride that is a multiple of 4 elements (got {addend.dtype} {tuple(addend.shape)} strides {tuple(addend.stride())})")
             addend = _aligned_addend(addend)                 # (a base that is not 8-byte aligned: through a copy, as in FusedLinear)
             ap, lda = addend.data_ptr(), (addend.stride(0) if self.M > 1 else self.N)      # (one row: any stride describes it)
@@ -1004,11 +990,11 @@ class ForwardPlan:
         if x.device != dev:
             raise RuntimeError(f"ForwardPlan: x lives on {x.device}, the plan was built for {dev}")
         if x.dtype != self.dtype or x.dim() != 2 or x.shape[0] != self.M or x.shape[1] != self.K or x.stride(1) != 1 or x.stride(0) != self.ldx:
-            raise RuntimeError(f"ForwardPlan: x must be {str(self.dtype).replace('torch.', '')} [{self.M}, {self.K}] with row stride {self.ldx} and a contiguous last dimension "
+            raise RuntimeError(f"ForwardPlan: x must be {_dtype_name(self.dtype)} [{self.M}, {self.K}] with row stride {self.ldx} and a contiguous last dimension "
                                f"(got {x.dtype} {tuple(x.shape)} strides {tuple(x.stride())})")
         q = torch.empty(self.q_shape, dtype=self.q_dtype, device=dev)
         y = torch.empty((self.M, self.N), dtype=self.dtype, device=dev)
-        xo = torch.empty((self.M, self.ldxo), dtype=self.dtype, device=dev) if self.ldxo else None
+        xo = torch.empty((self.M, self.ldxo), dtype=self.dtype, device=dev) if self.ldxo else None      # (ldxo: padded when the plan was built)
         if not self.captured and torch.cuda.is_current_stream_capturing():
             self.captured = True
         a = self.args
@@ -1022,7 +1008,7 @@ class ForwardPlan:
                 a.x_out = xo.data_ptr()
             a.x, a.q_x, a.y = x.data_ptr(), q.data_ptr(), y.data_ptr()
             rc = self.fn(self.ref, torch.cuda.current_stream(dev).cuda_stream)
-        if rc != 0:
+        if rc != 0:                                          # (the hot path calls the resolved function itself: no wrapper between)
             raise _capi.MixqError(self.fn_name, rc)
         q._mixq_fmt = self.qfmt
         return y, q, (xo[:, :self.n] if xo is not None else None)
@@ -1064,28 +1050,12 @@ def RMSNormQuantFused(x, weight, out, eps, ind, x_scale, bit, sigma=6.0, flag=No
     fmt = _want_fmt(packed, fmt)
     K = x.shape[-1]
     x2, o2 = x.reshape(-1, K), out.reshape(-1, K)
-    xp, ldx = _rows(x2, "x")
+    xrows = _rows(x2, "x")
     op, ldo = _rows(o2, "out")
-    M = x2.shape[0]
-    if x_scale.numel() < M:
-        raise RuntimeError(f"RMSNormQuantFused: x_scale holds {x_scale.numel()} rows, the batch has {M}")
-    n = 0 if ind is None else ind.numel()
-    q = torch.empty((packed_rows(M) if fmt else M, _q_row_bytes(K, bit, fmt)),
-                    dtype=torch.int8 if bit == 8 else torch.uint8, device=x.device)
-    if n:
-        ind = _check_ind(ind, "RMSNormQuantFused")
-        x_out = torch.empty((M, (n + 15) // 16 * 16), dtype=x.dtype, device=x.device)
-        xop, ldxo, ip = x_out.data_ptr(), x_out.stride(0), ind.data_ptr()
-    else:
-        x_out, xop, ldxo, ip = None, None, 0, None
-    if col_mask is not None and n:
-        _check_kept_map(col_mask, K, "RMSNormQuantFused")
-        _capi.call("mixq_rmsnorm_quant_fused_masked" + sfx, xp, weight.data_ptr(), op, ip, n, _ptr(n_dev), col_mask.data_ptr(), col_mask.numel(), x_scale.data_ptr(),
-                   q.data_ptr(), xop, _ptr(flag), M, K, ldx, ldo, ldxo, float(eps), bit, float(sigma), fmt, _stream())
-    else:
-        _capi.call("mixq_rmsnorm_quant_fused" + sfx, xp, weight.data_ptr(), op, ip, n, _ptr(n_dev), x_scale.data_ptr(), q.data_ptr(), xop,
-                   _ptr(flag), M, K, ldx, ldo, ldxo, float(eps), bit, float(sigma), fmt, _stream())
-    return set_fmt(q, fmt), (x_out[:, :n] if n else None)
+    if x_scale.numel() < x2.shape[0]:
+        raise RuntimeError(f"RMSNormQuantFused: x_scale holds {x_scale.numel()} rows, the batch has {x2.shape[0]}")
+    return _quant_pass("RMSNormQuantFused", "mixq_rmsnorm_quant_fused", sfx, x2, xrows, (weight.data_ptr(), op, ldo, eps), ind, x_scale, bit, sigma, None,
+                       flag, n_dev, fmt, col_mask)
 
 
 def layernorm_forward_cuda_extract_outliers(x, weight, out, eps, ind, x_scale):
@@ -1109,8 +1079,7 @@ def layernorm_forward_cuda_extract_outliers_int4(x, weight, out, eps, ind, x_sca
 # ------------------------------------------------------------------------------------------------------------
 def _w8a16_entry(name):
     """The bf16 twin of a W8A16 entry point (ABI 1.6), or a RuntimeError that says what is missing: no fall-back, no fp16 detour."""
-    if not hasattr(_capi.load(), name):
-        raise RuntimeError(f"mixq_amd.mixlib: {_capi.LIB_PATH} does not export {name} (the bfloat16 weight-only GEMM, ABI 1.6); rebuild it")
+    _capi.entry(name)
     return name
 
 
@@ -1125,7 +1094,7 @@ def PackW8A16(q_weight_kn, dtype=torch.float16):
     if dtype not in (torch.float16, torch.bfloat16):
         raise RuntimeError(f"PackW8A16: dtype must be torch.float16 or torch.bfloat16, got {dtype}")
     K, N = q_weight_kn.shape
-    out = torch.empty(((N + 15) // 16 * 16) * K, dtype=torch.uint8, device=q_weight_kn.device)
+    out = torch.empty(_pad16(N) * K, dtype=torch.uint8, device=q_weight_kn.device)
     name = "mixq_pack_w8a16" if dtype == torch.float16 else _w8a16_entry("mixq_pack_w8a16_bf16")
     _capi.call(name, q_weight_kn.data_ptr(), out.data_ptr(), K, N, _stream())
     out._mixq_w8a16_dtype = dtype
